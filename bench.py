@@ -13,6 +13,9 @@ collective is the final all_gather of the result latents (RCCL), inside the time
 
 Launch: `python bench.py` (1 GPU), `python bench.py --gpus N` (re-executes itself under torch.distributed.run with N ranks), or
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+A plain run sets up, warms up, times --steps calls and prints one JSON line (metric, value, unit, ms_per_step, ...).  `--full` adds
+what is measured beside the headline after the timed region (batch consistency, 1-scene latency, configs[2] / configs[3], VAE decode,
+per-op profile + roofline, CPU baseline); `--dump-outputs DIR` writes the last timed call's latents for output-by-output comparison.
 """
 import argparse
 import json
@@ -53,6 +56,10 @@ def pmc_traffic(kernel_name, avg_us=None):
     for k, v in rows.items():
         if kernel_name.startswith(k):
             cases = v.get("cases") or [v]
+            if "views" in _PMC:                 # nor counters of another batch: only cases profiled at the views of the plan timed here
+                cases = [c for c in cases if c.get("views") == _PMC["views"]]
+                if not cases:
+                    return None
             if avg_us is not None:      # several shapes of this kernel were profiled: report the one closest to the timed run's average launch
                 cases = sorted(cases, key=lambda c: abs((c.get("avg_us_profiled") or 0.0) - avg_us))
             best = dict(cases[0])
@@ -220,6 +227,21 @@ def cpu_baseline(cfg, n_steps_timed=3):
     return out
 
 
+DUMP_BUDGET_BYTES = 60_000_000       # the dump stays under 64 MB (10^6 bytes), .npy header included
+
+
+def dump_latents(out_dir, latents):
+    """--dump-outputs: the [scenes, ...] result as `out_dir/latents.npy` in float32.  Past DUMP_BUDGET_BYTES a fixed seeded sample of
+    scenes (in scene order), so that two runs with the same arguments dump the same rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, per_scene = latents.shape[0], latents[0].numel() * 4
+    if n * per_scene > DUMP_BUDGET_BYTES:
+        keep = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:max(1, DUMP_BUDGET_BYTES // per_scene)].sort().values
+        latents = latents[keep.to(latents.device)]
+    np.save(os.path.join(out_dir, "latents.npy"), latents.detach().float().cpu().numpy())
+
+
 def launcher_command(gpus, argv, port):
     """`python bench.py --gpus N` without a launcher becomes this command: one rank per GPU under torch.distributed.run, same flags."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
@@ -231,15 +253,25 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--scenes-per-gpu", type=int, default=192,
-                    help="scenes sampled per rank per pipe() call (throughput grows with the batch — fewer partial rounds of tiles: 6.33 / 6.46 / 6.53 "
-                         "scenes/s at 64 / 96 / 128 in round 2; round 4, two streams: 7.21 / 7.23 / 7.18 at 128 / 192 / 256; a 192-scene call takes 27 s)")
+    ap.add_argument("--scenes-per-gpu", type=int, default=64,
+                    help="scenes sampled per rank per pipe() call = one timed step (throughput grows with the batch — fewer partial rounds of tiles: "
+                         "5.41 / 6.94 / 7.46 / 7.49 / 7.70 scenes/s at 8 / 32 / 64 / 96 / 192, profiles/r07_bench_batch_sizes.log).  64 keeps a step at "
+                         "8.6 s, 3.1 %% below the 192-scene rate, so that a run of 25 steps takes 4 minutes, not 10.5; 192 is the batch of the round 1-6 "
+                         "records (tools/gpu_evidence.sh passes it)")
     ap.add_argument("--streams", type=int, default=0,
                     help="HIP streams a pipe() call spreads its scenes over (pipeline.streams: contiguous scene chunks, one plan + hipGraph each, "
                          "replayed concurrently; fills the tail / boundary gaps of whole-CU kernels); 0 = the library option STREAMS (csrc/options.h: 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run everything beside the headline figure: the batch-consistency check, the 1-scene latency, "
+                         "configs[2] / configs[3] / VAE decode side measurements, the per-op profile + roofline and the CPU baseline (the --no-* / "
+                         "--*-scenes / --side-runs / --ops-json options below tune these).  Off: set up, warm up, time --steps calls, print the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed region write what the last timed call returned as DIR/latents.npy (float32, [scenes, 6, 4, 28, 50] in "
+                         "global scene order; above 64 MiB a fixed seeded sample of scenes, kept in scene order).  Inputs and weights are seeded: "
+                         "two builds run with the same arguments can be compared output for output")
     ap.add_argument("--side-runs", action="store_true",
-                    help="with --gpus > 1: also run the side measurements (configs[2], configs[3], VAE decode); by default a multi-GPU run does the "
-                         "timed region only, so that N = 1, 2, 4, 8 back to back stay inside the driver's limit")
+                    help="with --full and --gpus > 1: also run the side measurements (configs[2], configs[3], VAE decode); by default a multi-GPU run "
+                         "does the timed region only, so that N = 1, 2, 4, 8 back to back stay inside a time limit")
     ap.add_argument("--pipe-factory", type=str, default="",
                     help="TEST HOOK (tests/test_distributed.py): 'module:function' returning (pipe, unet, cn) instead of the HIP pipeline, so that the "
                          "multi-rank control flow of this script (sharding, gather, timing, teardown, ONE JSON line) runs on a box without GPUs")
@@ -266,6 +298,10 @@ def main():
                     help="outside the timed region: decode this many scenes' latents with the HIP AutoencoderKL (VAE_SD15_CONFIG, random weights) — what output_type='np' "
                          "adds per scene (config.vae_decode_ms_per_scene, config.scenes_per_s_incl_vae_decode); 0 skips it")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.ops_json and not args.full:
+        ap.error("--ops-json needs --full (the per-op profile runs only there)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU over RCCL), same flags.  What the reference
@@ -293,7 +329,7 @@ def main():
         sync = torch.cuda.synchronize
     else:
         dev, n_devices, sync = torch.device("cpu"), world, (lambda: None)
-        args.no_op_profile = args.no_cpu_baseline = args.no_consistency_check = True
+        args.no_op_profile = args.no_cpu_baseline = True
         args.full_cond_scenes = args.hires_scenes = args.vae_scenes = 0
     if world > 1:                                               # N ranks generate 1.3 G random weights each on the host: share the cores
         torch.set_num_threads(max(4, (os.cpu_count() or 8) // world))
@@ -334,11 +370,13 @@ def main():
     dt = DD.max_over_ranks(time.perf_counter() - t0, dev)
     assert torch.isfinite(res).all(), "non-finite latents"
     scenes_per_s = n_total * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_latents(args.dump_outputs, res)
 
-    # ---- outside the timed region: is the measured configuration computing the same thing as the oracle-verified one? --------------
+    # ---- outside the timed region, --full only: is the measured configuration computing the same thing as the oracle-verified one? ----
     # Scenes are independent, so scene 0 of this rank's batch must reproduce a ONE-scene call on the same inputs (the configuration
     # tests/test_e2e_gpu.py::test_real_size_ddim_loop_sd15 checks against the CPU oracle) — whatever main loops the big batch routes to.
-    side = world == 1 or args.side_runs
+    side = args.full and (world == 1 or args.side_runs)
     consistency = None
     if not args.no_consistency_check and b > 1 and side:
         # first, middle and LAST scene of this rank's batch (the last one sits at the highest row indices: index arithmetic, 2 GiB windows)
@@ -476,8 +514,13 @@ def main():
                    {"workload": "configs[2]: 6-view 224x400, camera + 32 boxes + BEV map, CFG 2.0, same sampler", "scenes_per_gpu": full_cond["scenes_per_gpu"],
                     "seconds_per_call": round(full_cond["seconds_per_call"], 3)}},
     }
-    if not args.no_op_profile:
+    if args.full and not args.no_op_profile:
         fam, kern, rows = per_op_profile(plan)
+        _PMC["views"] = plan.B
+        summ = pmc_summary()
+        pviews = sorted({c.get("views") for v in (summ or {}).get("kernels", {}).values() for c in (v.get("cases") or [v])}, key=str)
+        if summ is not None and plan.B not in pviews:
+            _PMC["status"] += f"; its counters were collected at {pviews} views, the profiled plan has {plan.B}: counters dropped"
         out["config"]["per_op_profile"] = {"scenes": plan.b, "views": plan.B, "reps": 5, "statistic": "median (ms_best beside it in --ops-json)",
                                            "note": "one plan's step program launched op by op on ONE stream with HIP events between the launches"
                                                    + (f"; the timed region replays {pipe.streams} such plans concurrently" if pipe.streams > 1 and plan.b < b else "")}
@@ -538,7 +581,7 @@ def main():
             os.makedirs(os.path.dirname(args.ops_json) or ".", exist_ok=True)
             with open(args.ops_json, "w") as f:
                 json.dump(rows, f)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(cfg)
     print(json.dumps(out))
 

@@ -127,6 +127,62 @@ def test_bench_two_ranks_gloo_prints_one_json_line(tmp_path):
     assert out["config"]["full_cond_scenes_per_s"] is None and out["config"]["hires"] is None and "cpu_baseline" not in out
 
 
+def _bench_stub_run(tmp_path, factory, extra):
+    """bench.py --gpus 1 with a stubbed pipeline (no GPU): its one JSON line."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([root, os.path.join(root, "tests"), os.environ.get("PYTHONPATH", "")]),
+               CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="", OMP_NUM_THREADS="2")
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--scenes-per-gpu", "3", "--pipe-factory", f"bench_stub:{factory}"] + extra
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` with a stub whose result carries the number of the call: one JSON line
+    for 3 timed calls; DIR/latents.npy holds call 4 — the last timed one — as float32 in global scene order, identical across two runs."""
+    import numpy as np
+    from magicdrive_amd import synthetic
+    dumps = []
+    for k in range(2):
+        out = _bench_stub_run(tmp_path, "make_counting", ["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / f"run{k}")])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "scenes/s" and out["dtype"] == "bf16"
+        dumps.append(np.load(tmp_path / f"run{k}" / "latents.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (3, 6, 4, 28, 50)
+    assert np.array_equal(dumps[0], dumps[1])
+    lat = torch.cat([synthetic.make_scene_batch(1, seed=1234 + i, max_len=None, zero_map=True)["latents"] for i in range(3)])
+    assert np.array_equal(dumps[0][:, 5], (lat.float() * 2.0 + 4).numpy())
+
+
+def test_bench_side_checks_run_only_with_full(tmp_path):
+    """The batch-consistency check and the 1-scene latency run after the timed region with --full, and not in a plain run."""
+    plain = _bench_stub_run(tmp_path, "make", ["--steps", "1", "--warmup", "1"])
+    assert plain["config"]["batch_consistency_rel"] is None and plain["config"]["latency_1scene_s"] is None
+    full = _bench_stub_run(tmp_path, "make", ["--steps", "1", "--warmup", "1", "--full"])
+    assert full["config"]["batch_consistency_rel"] == 0.0 and full["config"]["latency_1scene_s"] is not None
+
+
+def test_bench_dump_outputs_seeded_sample_above_budget(tmp_path, monkeypatch):
+    """Past the dump budget the dump keeps a fixed seeded sample of scenes, in scene order, whatever run wrote it."""
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * 8 * 4)                # 10 scenes of 8 float32
+    x = torch.arange(40 * 8, dtype=torch.float64).reshape(40, 8)
+    for k in range(2):
+        bench.dump_latents(str(tmp_path / f"d{k}"), x)
+    a, b = np.load(tmp_path / "d0" / "latents.npy"), np.load(tmp_path / "d1" / "latents.npy")
+    assert a.dtype == np.float32 and a.shape == (10, 8) and np.array_equal(a, b)
+    rows = a[:, 0] / 8
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, x[torch.from_numpy(rows).long()].float().numpy())
+
+
 def _run_sample_driver(tmp_path, world, out_name, extra=()):
     import socket
     import subprocess

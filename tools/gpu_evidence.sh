@@ -10,7 +10,7 @@ rm -f $MDX_PARITY_LOG
 (timeout 1500 python -m pytest tests -m gpu -q --timeout 900 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.log)
 grep -E "passed|failed|error|rc=" $OUT/pytest_gpu.log | tail -4; grep -E "^FAILED|^ERROR" $OUT/pytest_gpu.log | head -20
 unset MDX_PARITY_LOG
-timeout 1500 python bench.py --steps ${BENCH_STEPS:-6} --warmup ${BENCH_WARMUP:-2} --ops-json $OUT/ops_b192.json > $OUT/bench_b192.json 2> $OUT/bench_b192.err; tail -c 600 $OUT/bench_b192.err; OUT=$OUT python - <<'PY'
+timeout 1500 python bench.py --full --scenes-per-gpu 192 --steps ${BENCH_STEPS:-6} --warmup ${BENCH_WARMUP:-2} --ops-json $OUT/ops_b192.json > $OUT/bench_b192.json 2> $OUT/bench_b192.err; tail -c 600 $OUT/bench_b192.err; OUT=$OUT python - <<'PY'
 import json, os
 d=json.load(open(os.environ['OUT']+'/bench_b192.json'))
 print({k:v for k,v in d.items() if k not in ('roofline','config','cpu_baseline')}); print(d['cpu_baseline']); print({k:v for k,v in d['config'].items() if k!='workload'})

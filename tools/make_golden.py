@@ -48,6 +48,9 @@ weights the HIP model holds — so that the fixture measures arithmetic, not wei
                     plain BEVControlNetConditioningEmbedding (tiny width).
   tiny_forward_nattn.pt  the reference UNet forward with neighboring_attn_type = concat and = self (same tiny weights and inputs).
   tiny_forward_zmod.pt   the reference UNet forward with zero_module_type = gated (GatedConnector) and = none (identity connector).
+  tiny_reference_checks.pt `... refchecks`  parameter shapes of the tiny reference modules; the reference pipeline's refusal of the stock
+                    DDIMScheduler (error, message, step() parameters); the reference UniPCMultistepScheduler on a
+                    fixed pseudo-model for four (steps, order, solver type) cases — what the oracle tests compare against without the reference.
 """
 import copy
 import time
@@ -435,9 +438,55 @@ def resolution_fixture(out_dir, cfg0, usd, meta, which):
     print(name, "eps std", e.std().item(), "down0 |x|", d[0].abs().mean().item(), "map", tuple(sc["bev_map"].shape))
 
 
+UNIPC_CASES = [(20, 2, "bh2"), (7, 2, "bh1"), (5, 1, "bh2"), (9, 3, "bh2")]
+
+
+def unipc_pseudo_model(x, t):
+    """The fixed pseudo-model tests/test_oracle.py::test_unipc_restatement_matches_live_reference drives both schedulers with."""
+    return torch.tanh(x * 0.7) + 0.1 * torch.cos(x * float(t) / 300)
+
+
+def reference_checks_fixture(out_dir):
+    """tiny_reference_checks.pt: the parameter shapes of the reference BEVControlNetModel / UNet2DConditionModelMultiview built at
+    spec.TINY_CONFIG (after a strict load of the seeded state dicts), and the reference environment's own UniPCMultistepScheduler run
+    on the pseudo-model above from seed-3 noise: timesteps and final sample for every (steps, order, solver type) case."""
+    from oracle import refshim
+    cfg = spec.TINY_CONFIG
+    usd, csd = state_dicts(cfg)
+    ns, unet, cnet = ref_models.build_reference(cfg, usd, csd)
+    shapes = {"unet": {k: tuple(v.shape) for k, v in unet.state_dict().items()},
+              "controlnet": {k: tuple(v.shape) for k, v in cnet.state_dict().items()}}
+    unipc = {}
+    for n, order, stype in UNIPC_CASES:
+        r = refshim.load().UniPCMultistepScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", solver_order=order,
+                                                   solver_type=stype)
+        r.set_timesteps(n)
+        x = torch.randn(2, 4, 6, 5, generator=torch.Generator().manual_seed(3))
+        for t in r.timesteps:
+            x = r.step(unipc_pseudo_model(x, t), t, x).prev_sample
+        unipc[f"{n},{order},{stype}"] = {"timesteps": r.timesteps.cpu().long().clone(), "x": x.float().clone()}
+    # the reference pipeline with the stock DDIMScheduler, whose step() takes `generator` (pipeline_bev_controlnet.py:94-97 refuses it)
+    import inspect
+    ns, pipe = ref_models.build_reference_pipeline(cfg, usd, csd)
+    pipe.scheduler = ns.DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", clip_sample=False, set_alpha_to_one=False, steps_offset=1)
+    sc = scene(cfg, 1, 2)
+    refusal = {"type": None, "message": None, "step_params": list(inspect.signature(pipe.scheduler.step).parameters)}
+    try:
+        pipe(prompt=None, image=sc["bev_map"], camera_param=sc["camera_param"], height=224, width=400, num_inference_steps=2,
+             guidance_scale=2.0, latents=sc["latents"], prompt_embeds=sc["prompt_embeds"], negative_prompt_embeds=sc["negative_prompt_embeds"],
+             output_type="latent", bev_controlnet_kwargs={"bboxes_3d_data": sc["bboxes_3d_data"]})
+    except Exception as e:
+        refusal.update(type=type(e).__name__, message=str(e))
+    torch.save({"param_shapes": shapes, "unipc": unipc, "unipc_seed": 3, "stock_ddim_refusal": refusal, "torch": str(torch.__version__)},
+               os.path.join(out_dir, "tiny_reference_checks.pt"))
+    print("tiny_reference_checks:", len(shapes["unet"]), "+", len(shapes["controlnet"]), "tensors,", len(unipc), "UniPC cases")
+
+
 def main():
     out_dir = os.path.join(ROOT, "tests", "golden")
     os.makedirs(out_dir, exist_ok=True)
+    if sys.argv[1:] == ["refchecks"]:
+        return reference_checks_fixture(out_dir)
     if sys.argv[1:] == ["sd15"]:
         return sd15_loop_fixture(out_dir, False)
     if sys.argv[1:] == ["sd15cfg"]:

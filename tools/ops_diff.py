@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Compare two per-op tables of the step program (`bench.py --ops-json`): per kernel and per op, which launches got slower / faster.
+"""Compare two per-op tables of the step program (`bench.py --full --ops-json`): per kernel and per op, which launches got slower / faster.
 A throughput number hides a slow kernel behind a fast one (round 3: +1 % end to end with layernorm_kernel 2.6x slower); this does not.
 Box-to-box spread is +-3-5 % on MFMA-bound kernels: pass --scale to normalise table B by the ratio of the two step totals.
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Speed-of-light table of the step program: for every launch max(FLOPs / MFMA peak, algorithmic bytes / HBM peak) next to the measured
-time (an --ops-json written by bench.py), summed per kernel.  The step is a mix of MFMA-bound launches (convs, attention, K >= 640
+time (an --ops-json written by bench.py --full), summed per kernel.  The step is a mix of MFMA-bound launches (convs, attention, K >= 640
 GEMMs) and HBM-bound ones (norms, the K = 320 projections, residual adds): this is the per-launch roofline the bench line's single
 `roofline` object cannot show.  CPU only: the plan is built on the host at a small batch and its activation bytes are scaled.
 Usage: python tools/sol_table.py profiles/r02e_ops_b128.json [--scenes 128] [--out profiles/r03_sol_table.json]
