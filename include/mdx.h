@@ -64,7 +64,18 @@ extern "C" {
  * current step's row of a table precomputed for all DDIM steps.
  * splitk: 0 = let the library choose (it splits K for small-M/huge-K shapes so the launch fills
  * 256 CUs), 1 = never, >1 = forced.  Splitting needs ws: fp32 [splitk][M][N] scratch of ws_bytes.
- * Requirements: K % 8 == 0, lda/ldw % 8 == 0, 16-byte aligned A/W; ldc,ldr % 4 == 0.
+ * Requirements (each checked on the host before anything is launched; a violation returns MDX_EINVAL and mdx_last_error() names the field):
+ *   - M, N, K, batch, rows_per_b, splitk fit a 32-bit int.
+ *   - K % 8 == 0; lda % 8 == 0 and ldw % 8 == 0; A and W 16-byte aligned (rows are read as 16-byte pieces).
+ *   - ldc % 4 == 0 and ldr % 4 == 0; C and R 8-byte aligned (16-bit C / R move as 8-byte pieces; the 16-byte epilogue is taken only when
+ *     N % 8 == 0, ldc, ldr, sC, sR % 8 == 0 and both pointers are 16-byte aligned — anything less is SERVED by the 8-byte epilogue).
+ *   - c_is_f32: C and R must be 16-byte aligned (fp32 rows move as float4, also in the split-K reduction).
+ *   - bias and temb must be 16-byte aligned, temb_sel_stride % 4 == 0 and temb_b_stride % 4 == 0 (read as float4); sel_ptr 4-byte aligned.
+ *   - ws must be 16-byte aligned (the split-K slabs are read as float4).  ws_bytes too small for the slabs reduces or disables the split
+ *     (SERVED); a split with ws_bytes > 0 and ws == NULL is refused.
+ *   - batch > 1: sA % 8 == 0, sW % 8 == 0, sC % 4 == 0, sR % 4 == 0.
+ *   - N % 4 != 0 needs a plain epilogue (no bias / temb / R / epilogue / forced split-K) and ldc >= roundup4(N).
+ *   - MDX_EPI_GEGLU needs N % 64 == 0.
  */
 typedef struct MdxGemmDesc {
     const void* A; const void* W; void* C; const void* R;
@@ -130,7 +141,12 @@ int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream);
  * residual add :638), Downsample2D (resnet.py:198-222), Upsample2D.conv (resnet.py:165-170),
  * the BEV map encoder (map_embedder.py:66-76).  Weights are pre-packed [Cout][kh][kw][Cin].
  * ldx/ldy/ldr: pixel strides in elements (a tensor may be a channel slice of a wider one).
- * Cin % 8 == 0 required (smaller Cin goes through mdx_conv2d_direct).
+ * Requirements (host-checked, MDX_EINVAL, the message names the field):
+ *   - Cin % 8 == 0 (smaller Cin goes through mdx_conv2d_direct) and Cout % 4 == 0; no GEGLU epilogue.
+ *   - every size field, Ho * Wo, B * Ho * Wo and kh * kw * Cin fit a 32-bit int.
+ *   - ldx % 8 == 0, X and Wt 16-byte aligned; ldy % 4 == 0 and ldr % 4 == 0, Y and R 8-byte aligned (the 16-byte epilogue is taken when
+ *     Cout, ldy, ldr % 8 == 0 and both are 16-byte aligned; less is served by the 8-byte one).
+ *   - bias and temb must be 16-byte aligned, temb_sel_stride % 4 == 0, temb_b_stride % 4 == 0; sel_ptr 4-byte aligned; ws 16-byte aligned.
  */
 typedef struct MdxConvDesc {
     const void* X; const void* Wt; void* Y; const void* R;
@@ -149,6 +165,10 @@ int mdx_conv2d_bf16(const MdxConvDesc* d, void* stream);
  * (fp32 accumulate): conv_in (Cin=4, unet_2d_condition.py:262-265), conv_out (Cout=4, :497-500),
  * cam2token (K=189, unet_addon_rawbox.py:106), bbox_proj (K=216, bbox_embedder.py:72).
  * x_is_f32 / y_is_f32 select fp32 I/O (latents and eps stay fp32).
+ * Served at every alignment: operands need only their element's natural alignment (2 bytes for 16-bit, 4 for fp32 X / Y / R / bias / temb /
+ * sel_ptr); the 16-byte K-parallel kernels are taken for a 16-bit X (x_is_f32 == 0) when Cout <= 8, Cin % 8 == 0, ldx % 8 == 0, kh * kw * Cin >= 512 and X, Wt are 16-byte
+ * aligned, the one-thread-per-output kernel otherwise.  Requirements (MDX_EINVAL): natural alignment as above; no GEGLU epilogue; every size
+ * field, Ho * Wo, B * Ho * Wo and kh * kw * Cin must fit a 32-bit int.
  */
 typedef struct MdxConvDirectDesc {
     const void* X; const void* Wt; void* Y; const void* R;
@@ -175,7 +195,13 @@ int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream);
  *     blocks.py:112-121, 213-217 (left + right neighbour; the doubled out-bias is the caller's business);
  *   joint == 1, nsrc ∈ {1..8}: ONE softmax over the concatenation of the sources' keys — "concat" (the two neighbours, blocks.py:122-134)
  *     and "self" (all cameras of the scene, blocks.py:135-138).
- * d % 8 == 0, d <= 160; ldq,ldk,ldv,sQ,sK,sV % 8 == 0; ldo % 4 == 0.
+ * Requirements (host-checked, MDX_EINVAL, the message names the field):
+ *   - d % 8 == 0, 0 < d <= 160.  Kernel instances exist for ceil(d / 16) in {1..6, 8, 10}, a ragged last 16-column chunk is masked:
+ *     SUPPORTED d = 8 .. 96 (every multiple of 8), 120, 128, 152, 160;  d = 104, 112, 136, 144 return MDX_EUNSUPPORTED.
+ *   - ldq, ldk, ldv, sQ, sK, sV must be multiples of 8 and Q, K, Vt 16-byte aligned (rows are read as 16-byte pieces); ldv >= Tk.
+ *   - ldo % 4 == 0, sO % 4 == 0 and O must be 8-byte aligned (an O row is written as 8-byte pieces — ldo % 8 == 4 is served).
+ *   - B, H, Tq, Tk fit a 32-bit int; joint must be 0 or 1; nsrc must be 1..2 (joint: 1..8); nsrc > 1 needs a kvmap (4-byte aligned);
+ *     q_prescaled must be 0 or 1.
  */
 typedef struct MdxAttnDesc {
     const void* Q; const void* K; const void* Vt; void* O;
@@ -195,6 +221,12 @@ int mdx_attention_bf16(const MdxAttnDesc* d, void* stream);
  * (ATen native_group_norm + silu: resnet.py:596-598, 626-630; transformer_2d.py:278;
  *  unet_2d_condition_multiview.py:519-521).  Statistics in fp32, pivot-shifted / Chan-combined (no E[x^2]-E[x]^2
  * cancellation); with a workspace, large maps take a two-stage fully coalesced path (deterministic, no atomics).
+ * Served: X / Y at any 2-byte alignment and any ldx, ldy >= C — the one-launch kernel picks a vector width of 8, 4, 2 or 1 elements from
+ * C / G, ldx, ldy and the two pointers; the two-stage path is taken only for C % 8 == 0, ldx, ldy % 8 == 0 and 16-byte aligned X / Y.
+ * Requirements (MDX_EINVAL): G > 0 and C % G == 0; 0 < C <= ldx, ldy; B, HW, C, G fit a 32-bit int; gamma, beta must be 16-byte aligned
+ * (read as float4); ws, when given, must be 16-byte aligned.
+ * MDX_EUNSUPPORTED: more than 2560 channels per group on the one-launch kernel (its LDS gamma / beta table) — such a group is served only
+ * where the two-stage path applies (workspace given, C % 8 == 0, C <= 5120, aligned, more than GN_ONE_KERNEL_ELEMS elements).
  */
 typedef struct MdxGroupNormDesc {
     const void* X; void* Y; const float* gamma; const float* beta;
@@ -205,7 +237,9 @@ typedef struct MdxGroupNormDesc {
 } MdxGroupNormDesc;
 int mdx_groupnorm_bf16(const MdxGroupNormDesc* d, void* stream);
 
-/* mdx_layernorm_bf16 — LayerNorm over the last dim of [M][C] (attention.py:85,104,120; blocks.py:67-71). */
+/* mdx_layernorm_bf16 — LayerNorm over the last dim of [M][C] (attention.py:85,104,120; blocks.py:67-71).
+ * Requirements (MDX_EINVAL): C, ldx, ldy must be multiples of 8, 0 < C <= ldx, ldy; X, Y, gamma, beta must be 16-byte aligned (rows move as
+ * 16-byte pieces, gamma / beta as float4); M fits a 32-bit int.  C > 2048 returns MDX_EUNSUPPORTED. */
 typedef struct MdxLayerNormDesc {
     const void* X; void* Y; const float* gamma; const float* beta;
     int64_t M, C, ldx, ldy;
@@ -217,7 +251,8 @@ int mdx_layernorm_bf16(const MdxLayerNormDesc* d, void* stream);
 /* mdx_softmax_rows — Y[r][0..T) = softmax(scale * X[r][0..T)) row by row, fp32 in (the fp32 scores of a Q K^T GEMM), bf16 out;
  * columns T..ldy-1 of Y are written as zeros (so Y can be the K-padded A operand of the P V GEMM).  Used by the VAE decoder's
  * single-head, 512-channel mid-block attention (attention_processor.py:495-558 with upcast_softmax; unet_2d_blocks.py:433-445),
- * whose head dim is outside the fused attention kernel's range. */
+ * whose head dim is outside the fused attention kernel's range.
+ * Requirements (MDX_EINVAL): 0 < T <= ldx, ldy; rows, T, ldy fit a 32-bit int; X 4-byte, Y 2-byte aligned (element accesses only). */
 typedef struct MdxSoftmaxDesc {
     const float* X; void* Y;
     int64_t rows, T, ldx, ldy;
@@ -234,6 +269,10 @@ int mdx_softmax_rows(const MdxSoftmaxDesc* d, void* stream);
 #define MDX_EW_NHWC_TO_NCHW 5
 #define MDX_EW_SILU 6
 #define MDX_EW_SCALE 7        /* Y = X * alpha */
+/* Served at every alignment: X / Y need their element's natural alignment only (2 bytes, 4 for fp32), any ldx / ldy; the 16-byte kernels
+ * (ew_vec8_kernel, ew_upsample_vec8_kernel) are taken for 16-bit X and Y with C % 8 == 0, ldx, ldy % 8 == 0 and 16-byte aligned pointers,
+ * ew_scalar_kernel otherwise.  Requirements (MDX_EINVAL): a known kind; natural alignment; C, B, Hi, Wi, Ho, Wo fit a 32-bit int;
+ * MDX_EW_UPSAMPLE needs ymap / xmap. */
 typedef struct MdxEwDesc {
     const void* X; void* Y; const int32_t* ymap; const int32_t* xmap;
     int64_t kind, M, C, ldx, ldy;
@@ -248,6 +287,7 @@ int mdx_elementwise(const MdxEwDesc* d, void* stream);
  * (magicdrive/networks/embedder.py:15-40) for camera columns (unet_addon_rawbox.py:288-305) and
  * box corners with the masked null blend pos*m + null*(1-m) (bbox_embedder.py:165-176).
  *   X fp32 [n][P][3]  ->  Y bf16 [n][P*(3+6F)] ; mask (uint8 [n]) and null (fp32 [P*(3+6F)]) optional.
+ * Requirements (MDX_EINVAL): 0 <= F <= 16; P fits a 32-bit int; natural alignment of X, null_feat (4) and Y (2).  Element accesses only.
  */
 typedef struct MdxFourierDesc {
     const float* X; void* Y; const uint8_t* mask; const float* null_feat;
@@ -258,6 +298,7 @@ int mdx_fourier_embed(const MdxFourierDesc* d, void* stream);
 /*
  * mdx_gather_rows — Y[i,:] = m[i] ? T[idx[i],:] : null[:]  (class-token lookup with null blend,
  * bbox_embedder.py:179-180; idx may be -1 where mask is 0).
+ * Requirements (MDX_EINVAL): C and n_rows fit a 32-bit int, n_rows must be positive; idx 8-byte aligned, T / Y / null_row 2-byte aligned.
  */
 typedef struct MdxGatherDesc {
     const void* T; void* Y; const int64_t* idx; const uint8_t* mask; const void* null_row; void* reserved_p;
@@ -269,6 +310,7 @@ int mdx_gather_rows(const MdxGatherDesc* d, void* stream);
  * mdx_timestep_embedding — sinusoidal timestep features, fp32 math
  * (diffusers/models/embeddings.py:24-64 with flip_sin_to_cos, downscale_freq_shift):
  *   Y[i, :] = [cos(t_i * f_j) | sin(t_i * f_j)]  (flip) , f_j = exp(-ln(max_period) * j / (half - shift))
+ * Requirements (MDX_EINVAL): dim fits a 32-bit int, ldy >= dim; t and Y 4-byte aligned.
  */
 typedef struct MdxTimeEmbDesc {
     const float* t; float* Y;   /* Y fp32 [n][ldy] */
@@ -289,6 +331,9 @@ int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream);
  *   xin_ld == 0 : x_in is fp32, flat, same layout as x;
  *   xin_ld  > 0 : x_in is bf16 channels-last with pixel stride xin_ld >= xin_c (x has xin_c channels per
  *                 pixel; the pad channels are never written) — the layout conv_in's MFMA path reads.
+ * Requirements (MDX_EINVAL; the same hold for mdx_cfg_unipc_step): x, eps, coef, step_ptr 4-byte aligned; xin_c, xin_ld, gv_last_step fit a
+ * 32-bit int; xin_ld > 0 needs 0 < xin_c <= xin_ld and xin_c dividing n; a given-view mode needs gv_noise (mode 1: also gv_cond) and
+ * gv_view_elems dividing n.
  */
 typedef struct MdxDdimDesc {
     float* x; const float* eps; const float* coef; int32_t* step_ptr; void* x_in; void* reserved_p;
@@ -383,7 +428,8 @@ int mdx_cfg_unipc_step_f16(const MdxUniPCDesc* d, void* stream);
 int mdx_softmax_rows_f16(const MdxSoftmaxDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
- * mdx_last_error() names the op index). */
+ * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each
+ * requirement listed above holds here and for the _f16 symbols unchanged. */
 int mdx_program_run(const MdxOp* ops, int64_t n, void* stream);
 
 /* Capture ops[0..n) into a hipGraph (stream capture on an internal stream) and instantiate it.

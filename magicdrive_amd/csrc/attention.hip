@@ -361,23 +361,31 @@ using namespace mdx;
 
 extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
     if (!a || !a->Q || !a->K || !a->Vt || !a->O) return set_error(MDX_EINVAL, "mdx_attention_bf16: null operand");
-    if (a->d % 8 || a->d <= 0 || a->d > 160) return set_error(MDX_EINVAL, "head dim %ld unsupported (d %% 8 == 0, d <= 160)", (long)a->d);
+    const char* op = "mdx_attention_bf16";
+    if (a->d % 8 || a->d <= 0 || a->d > 160) return set_error(MDX_EINVAL, "head dim d=%ld unsupported (d %% 8 == 0, d <= 160)", (long)a->d);
+    {   // kernel instances exist for 1-6, 8 and 10 chunks of 16 columns (a ragged last chunk is masked): d in (96, 112] and (128, 144] has none
+        const int d16 = (int)(a->d + 15) / 16;
+        if (d16 == 7 || d16 == 9) return set_error(MDX_EUNSUPPORTED, "head dim d=%ld: no kernel instance (d/16 = %d)", (long)a->d, d16);
+    }
     if (a->joint != 0 && a->joint != 1) return set_error(MDX_EINVAL, "joint must be 0 or 1");
     if (a->nsrc < 1 || a->nsrc > (a->joint ? 8 : 2)) return set_error(MDX_EINVAL, "nsrc must be 1 or 2 (joint: 1..8)");
     if (a->nsrc > 1 && !a->kvmap) return set_error(MDX_EINVAL, "nsrc > 1 needs a kvmap");
-    if ((a->ldq % 8) || (a->ldk % 8) || (a->ldv % 8) || (a->sQ % 8) || (a->sK % 8) || (a->sV % 8) || (a->ldo % 4) || (a->sO % 4))
-        return set_error(MDX_EINVAL, "attention strides must be multiples of 8 (Q,K,Vt) / 4 (O)");
-    if (((uintptr_t)a->Q & 15) || ((uintptr_t)a->K & 15) || ((uintptr_t)a->Vt & 15) || ((uintptr_t)a->O & 7))
-        return set_error(MDX_EINVAL, "attention operands must be 16-byte aligned");
+    MDX_NEED(need_int(op, "B", a->B)); MDX_NEED(need_int(op, "H", a->H)); MDX_NEED(need_int(op, "Tq", a->Tq)); MDX_NEED(need_int(op, "Tk", a->Tk));
+    // Q / K rows and V^T rows are read as 16-byte pieces; an O row is written as 8-byte pieces (4 head-dim columns of one query)
+    MDX_NEED(need_multiple(op, "ldq", a->ldq, 8)); MDX_NEED(need_multiple(op, "ldk", a->ldk, 8)); MDX_NEED(need_multiple(op, "ldv", a->ldv, 8));
+    MDX_NEED(need_multiple(op, "sQ", a->sQ, 8)); MDX_NEED(need_multiple(op, "sK", a->sK, 8)); MDX_NEED(need_multiple(op, "sV", a->sV, 8));
+    MDX_NEED(need_multiple(op, "ldo", a->ldo, 4)); MDX_NEED(need_multiple(op, "sO", a->sO, 4));
+    MDX_NEED(need_aligned(op, "Q", a->Q, 16)); MDX_NEED(need_aligned(op, "K", a->K, 16)); MDX_NEED(need_aligned(op, "Vt", a->Vt, 16));
+    MDX_NEED(need_aligned(op, "O", a->O, 8)); MDX_NEED(need_aligned(op, "kvmap", a->kvmap, 4));
+    if (a->q_prescaled != 0 && a->q_prescaled != 1) return set_error(MDX_EINVAL, "q_prescaled must be 0 or 1");
+    if (a->Tk > 0 && a->ldv < a->Tk) return set_error(MDX_EINVAL, "ldv < Tk");
     if (a->Tq <= 0 || a->Tk <= 0 || a->B <= 0 || a->H <= 0) return MDX_OK;
-    if (a->ldv < a->Tk) return set_error(MDX_EINVAL, "ldv < Tk");
     AttnParams p;
     p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.Vt = (const bf16_t*)a->Vt; p.O = (bf16_t*)a->O;
     p.kvmap = a->kvmap;
     p.B = (int)a->B; p.H = (int)a->H; p.Tq = (int)a->Tq; p.Tk = (int)a->Tk; p.d = (int)a->d; p.nsrc = (int)a->nsrc; p.joint = (int)a->joint;
     p.ldq = a->ldq; p.sQ = a->sQ; p.ldk = a->ldk; p.sK = a->sK; p.ldv = a->ldv; p.sV = a->sV; p.ldo = a->ldo; p.sO = a->sO;
     // q_prescaled: the caller folded scale * log2(e) into the query projection: scores are base-2 exponents already
-    if (a->q_prescaled != 0 && a->q_prescaled != 1) return set_error(MDX_EINVAL, "q_prescaled must be 0 or 1");
     p.scale_log2 = a->q_prescaled ? 1.0f : (float)(a->scale * 1.4426950408889634);
     hipStream_t st = (hipStream_t)stream;
     {

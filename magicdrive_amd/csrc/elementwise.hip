@@ -486,6 +486,20 @@ using namespace mdx;
 extern "C" int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream) {
     if (!d || !d->X || !d->Wt || !d->Y) return set_error(MDX_EINVAL, "mdx_conv2d_direct: null operand");
     if (d->epilogue == MDX_EPI_GEGLU) return set_error(MDX_EINVAL, "direct conv has no GEGLU epilogue");
+    const char* op = "mdx_conv2d_direct";
+    MDX_NEED(need_int(op, "B", d->B)); MDX_NEED(need_int(op, "Hi", d->Hi)); MDX_NEED(need_int(op, "Wi", d->Wi)); MDX_NEED(need_int(op, "Cin", d->Cin));
+    MDX_NEED(need_int(op, "Ho", d->Ho)); MDX_NEED(need_int(op, "Wo", d->Wo)); MDX_NEED(need_int(op, "Cout", d->Cout));
+    MDX_NEED(need_int(op, "kh", d->kh)); MDX_NEED(need_int(op, "kw", d->kw)); MDX_NEED(need_int(op, "sh", d->sh)); MDX_NEED(need_int(op, "sw", d->sw));
+    MDX_NEED(need_int(op, "ph", d->ph)); MDX_NEED(need_int(op, "pw", d->pw));
+    if (d->B < 0 || d->Ho < 0 || d->Wo < 0 || d->kh < 0 || d->kw < 0 || d->Cin < 0) return set_error(MDX_EINVAL, "%s: negative size", op);
+    MDX_NEED(need_int(op, "Ho * Wo", d->Ho * d->Wo));
+    MDX_NEED(need_int(op, "B * Ho * Wo", d->B * (d->Ho * d->Wo)));
+    MDX_NEED(need_int(op, "kh * kw", d->kh * d->kw));
+    MDX_NEED(need_int(op, "kh * kw * Cin", d->kh * d->kw * d->Cin));
+    // every operand is served at its element's natural alignment (the 16-byte K-parallel kernels are chosen by alignment below)
+    MDX_NEED(need_aligned(op, "X", d->X, d->x_is_f32 ? 4 : 2)); MDX_NEED(need_aligned(op, "Wt", d->Wt, 2));
+    MDX_NEED(need_aligned(op, "Y", d->Y, d->y_is_f32 ? 4 : 2)); MDX_NEED(need_aligned(op, "R", d->R, d->y_is_f32 ? 4 : 2));
+    MDX_NEED(need_aligned(op, "bias", d->bias, 4)); MDX_NEED(need_aligned(op, "temb", d->temb, 4)); MDX_NEED(need_aligned(op, "sel_ptr", d->sel_ptr, 4));
     CDParams p;
     p.X = d->X; p.W = (const bf16_t*)d->Wt; p.Y = d->Y; p.R = d->R; p.bias = d->bias; p.temb = d->temb; p.sel = d->sel_ptr;
     p.B = (int)d->B; p.Hi = (int)d->Hi; p.Wi = (int)d->Wi; p.Cin = (int)d->Cin; p.Ho = (int)d->Ho; p.Wo = (int)d->Wo; p.Cout = (int)d->Cout;
@@ -520,6 +534,12 @@ extern "C" int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream) {
 
 extern "C" int mdx_elementwise(const MdxEwDesc* d, void* stream) {
     if (!d || !d->X || !d->Y) return set_error(MDX_EINVAL, "mdx_elementwise: null operand");
+    const char* op = "mdx_elementwise";
+    MDX_NEED(need_int(op, "C", d->C)); MDX_NEED(need_int(op, "B", d->B)); MDX_NEED(need_int(op, "Hi", d->Hi)); MDX_NEED(need_int(op, "Wi", d->Wi));
+    MDX_NEED(need_int(op, "Ho", d->Ho)); MDX_NEED(need_int(op, "Wo", d->Wo));
+    // served at the element's natural alignment: the 16-byte kernels are chosen by C % 8, the strides and the pointers below
+    MDX_NEED(need_aligned(op, "X", d->X, d->x_is_f32 ? 4 : 2)); MDX_NEED(need_aligned(op, "Y", d->Y, d->y_is_f32 ? 4 : 2));
+    MDX_NEED(need_aligned(op, "ymap", d->ymap, 4)); MDX_NEED(need_aligned(op, "xmap", d->xmap, 4));
     EWParams p;
     p.X = d->X; p.Y = d->Y; p.ymap = d->ymap; p.xmap = d->xmap; p.kind = (int)d->kind; p.M = d->M; p.C = (int)d->C;
     p.ldx = d->ldx; p.ldy = d->ldy; p.B = (int)d->B; p.Hi = (int)d->Hi; p.Wi = (int)d->Wi; p.Ho = (int)d->Ho; p.Wo = (int)d->Wo;
@@ -556,6 +576,9 @@ extern "C" int mdx_elementwise(const MdxEwDesc* d, void* stream) {
 extern "C" int mdx_fourier_embed(const MdxFourierDesc* d, void* stream) {
     if (!d || !d->X || !d->Y) return set_error(MDX_EINVAL, "mdx_fourier_embed: null operand");
     if (d->F < 0 || d->F > 16) return set_error(MDX_EINVAL, "fourier: F out of range");
+    MDX_NEED(need_int("mdx_fourier_embed", "P", d->P));
+    MDX_NEED(need_aligned("mdx_fourier_embed", "X", d->X, 4)); MDX_NEED(need_aligned("mdx_fourier_embed", "Y", d->Y, 2));
+    MDX_NEED(need_aligned("mdx_fourier_embed", "null_feat", d->null_feat, 4));
     FourierParams p{d->X, (bf16_t*)d->Y, d->mask, d->null_feat, d->n, (int)d->P, (int)d->F, d->ldy};
     long total = p.n * p.P * (3 + 6 * p.F);
     if (total <= 0) return MDX_OK;
@@ -565,6 +588,10 @@ extern "C" int mdx_fourier_embed(const MdxFourierDesc* d, void* stream) {
 
 extern "C" int mdx_gather_rows(const MdxGatherDesc* d, void* stream) {
     if (!d || !d->T || !d->Y || !d->idx) return set_error(MDX_EINVAL, "mdx_gather_rows: null operand");
+    MDX_NEED(need_int("mdx_gather_rows", "C", d->C)); MDX_NEED(need_int("mdx_gather_rows", "n_rows", d->n_rows));
+    MDX_NEED(need_aligned("mdx_gather_rows", "T", d->T, 2)); MDX_NEED(need_aligned("mdx_gather_rows", "Y", d->Y, 2));
+    MDX_NEED(need_aligned("mdx_gather_rows", "idx", d->idx, 8)); MDX_NEED(need_aligned("mdx_gather_rows", "null_row", d->null_row, 2));
+    if (d->n_rows <= 0 && d->n > 0 && d->C > 0) return set_error(MDX_EINVAL, "mdx_gather_rows: n_rows must be positive");
     GatherParams p{(const bf16_t*)d->T, (bf16_t*)d->Y, d->idx, d->mask, (const bf16_t*)d->null_row, d->n, (int)d->C, d->ldt, d->ldy, (int)d->n_rows};
     long total = p.n * p.C;
     if (total <= 0) return MDX_OK;
@@ -574,6 +601,9 @@ extern "C" int mdx_gather_rows(const MdxGatherDesc* d, void* stream) {
 
 extern "C" int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream) {
     if (!d || !d->t || !d->Y) return set_error(MDX_EINVAL, "mdx_timestep_embedding: null operand");
+    MDX_NEED(need_int("mdx_timestep_embedding", "dim", d->dim));
+    MDX_NEED(need_aligned("mdx_timestep_embedding", "t", d->t, 4)); MDX_NEED(need_aligned("mdx_timestep_embedding", "Y", d->Y, 4));
+    if (d->dim > 0 && d->ldy < d->dim) return set_error(MDX_EINVAL, "mdx_timestep_embedding: ldy < dim");
     TimeEmbParams p{d->t, d->Y, d->n, (int)d->dim, (int)d->flip_sin_to_cos, d->ldy, (float)d->freq_shift, (float)d->max_period, 1};
     long total = p.n * p.dim;
     if (total <= 0) return MDX_OK;
@@ -583,6 +613,9 @@ extern "C" int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream) {
 
 extern "C" int mdx_cfg_ddim_step(const MdxDdimDesc* d, void* stream) {
     if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr) return set_error(MDX_EINVAL, "mdx_cfg_ddim_step: null operand");
+    MDX_NEED(need_int("mdx_cfg_ddim_step", "xin_c", d->xin_c)); MDX_NEED(need_int("mdx_cfg_ddim_step", "xin_ld", d->xin_ld)); MDX_NEED(need_int("mdx_cfg_ddim_step", "gv_last_step", d->gv_last_step));
+    MDX_NEED(need_aligned("mdx_cfg_ddim_step", "x", d->x, 4)); MDX_NEED(need_aligned("mdx_cfg_ddim_step", "eps", d->eps, 4)); MDX_NEED(need_aligned("mdx_cfg_ddim_step", "coef", d->coef, 4));
+    MDX_NEED(need_aligned("mdx_cfg_ddim_step", "step_ptr", d->step_ptr, 4));
     DdimParams p{d->x, d->eps, d->coef, d->step_ptr, d->x_in, d->n, (int)d->cfg, (float)d->guidance, (int)d->xin_c, (int)d->xin_ld,
                  d->gv_cond, d->gv_noise, d->gv_mask, d->gv_mask ? (int)d->gv_mode : 0, d->gv_view_elems, (int)d->gv_last_step};
     if (p.xin_ld > 0 && (p.xin_c <= 0 || p.xin_ld < p.xin_c || p.n % p.xin_c)) return set_error(MDX_EINVAL, "ddim: bad x_in channel layout");
@@ -600,6 +633,9 @@ extern "C" int mdx_cfg_ddim_step(const MdxDdimDesc* d, void* stream) {
 extern "C" int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream) {
     if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr || !d->x_last || !d->m1 || !d->m2)
         return set_error(MDX_EINVAL, "mdx_cfg_unipc_step: null operand");
+    MDX_NEED(need_int("mdx_cfg_unipc_step", "xin_c", d->xin_c)); MDX_NEED(need_int("mdx_cfg_unipc_step", "xin_ld", d->xin_ld)); MDX_NEED(need_int("mdx_cfg_unipc_step", "gv_last_step", d->gv_last_step));
+    MDX_NEED(need_aligned("mdx_cfg_unipc_step", "x", d->x, 4)); MDX_NEED(need_aligned("mdx_cfg_unipc_step", "eps", d->eps, 4)); MDX_NEED(need_aligned("mdx_cfg_unipc_step", "coef", d->coef, 4));
+    MDX_NEED(need_aligned("mdx_cfg_unipc_step", "step_ptr", d->step_ptr, 4));
     UniPCParams p{d->x, d->eps, d->coef, d->step_ptr, d->x_in, d->x_last, d->m1, d->m2, d->n, (int)d->cfg, (float)d->guidance, (int)d->xin_c, (int)d->xin_ld,
                   d->gv_cond, d->gv_noise, d->gv_mask, d->gv_mask ? (int)d->gv_mode : 0, d->gv_view_elems, (int)d->gv_last_step};
     if (p.xin_ld > 0 && (p.xin_c <= 0 || p.xin_ld < p.xin_c || p.n % p.xin_c)) return set_error(MDX_EINVAL, "unipc: bad x_in channel layout");

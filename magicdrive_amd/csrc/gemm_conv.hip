@@ -371,6 +371,7 @@ template <int BM, int BN, int BK, int WM, int WN, bool CONV, bool PIPE>
 static int launch_one_(const GCParams& p, hipStream_t st) {
     constexpr size_t ring = (size_t)2 * (BM + BN) * (BK + 8) * sizeof(bf16_t), ctile = (size_t)BM * (BN + 8) * 2;
     constexpr size_t smem = ring > ctile ? ring : ctile;
+    if (p.rowstat) return set_error(MDX_EINVAL, "gemm_conv_kernel: rowstat_out reached a route that does not emit row statistics");
     auto kern = gemm_conv_kernel<BM, BN, BK, WM, WN, CONV, PIPE>;
     if (int rc = ensure_dyn_smem((const void*)kern, smem, "gemm_conv")) return rc;
     GCParams q = p;
@@ -414,20 +415,6 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
                  (!p.R || ((p.ldr % 8) == 0 && (p.sR % 8) == 0 && (((uintptr_t)p.R) & 15) == 0));
     }
     if (!opt(OPT_LN_STATS)) { p.rowstat = nullptr; p.rowstat_parts = 0; p.ln_stats = nullptr; p.ln_stats_parts = 0; }   // A/B: the round-5 data flow
-    if (p.rowstat) {
-        // Row statistics of C for the LayerNorm that reads it next (MdxGemmDesc.rowstat_out): the K = 320 weight-stationary kernel emits them
-        // from its store phase; every other route gets them from a small kernel over the finished C (part 0 = whole rows, the rest zeros).
-        if (conv || p.batch > 1 || p.epi != 0 || p.c_f32 || p.Vt || p.rowstat_parts < 1) return set_error(MDX_EINVAL, "rowstat_out: plain 2-D GEMM with 16-bit C only");
-        const int ws_mode_ = (int)opt(OPT_GEMM_WS);
-        const bool ws_route = ws_mode_ > 0 && p.splitk <= 1 && ws_supported(p) && (ws_mode_ >= 2 || p.M >= 8192) &&
-                              !((int)opt(OPT_XL_K320) && (int)opt(OPT_GEMM_XL) > 0) && (int)opt(OPT_GEMM_XL) < 2;
-        if (!(ws_route && ws_emits_rowstat(p) && opt(OPT_LN_FUSE))) {
-            GCParams q = p;
-            q.rowstat = nullptr; q.rowstat_parts = 0;
-            if (int rc = launch_gemm_conv(q, conv, st)) return rc;
-            return launch_rowstat((const bf16_t*)p.C, p.M, p.N, p.ldc, p.rowstat, p.rowstat_parts, st);
-        }
-    }
     if (geglu && (p.N % 64) != 0) return set_error(MDX_EINVAL, "GEGLU needs packed N %% 64 == 0 (N=%d)", p.N);
     constexpr int impl = 0;
     // K = 320 projections with many rows: weights in registers, activations streamed (gemm_ws.hip).  MDX_GEMM_WS: 0 off, 1 when
@@ -439,6 +426,28 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
     const int xl_mode = (int)opt(OPT_GEMM_XL);
     const int xl_k320 = (int)opt(OPT_XL_K320);
     const int xl_min_tiles = (int)opt(OPT_XL_MIN_TILES);
+    // K = 320 GEGLU with many rows: gemm_ws.hip (384 views: 1642 us) vs the 256 x 256 XL tile (1694-1757 us).  Before the ring of
+    // gemm_ws.hip really ran ahead (its DMA builtin drained the VM counter every slab: 1994 us) the XL tile was the faster one;
+    // MDX_XL_GEGLU320=1 selects it again.
+    const int xl_geglu320 = (int)opt(OPT_XL_GEGLU320);
+    const bool geglu_xl = xl_geglu320 && xl_mode == 1 && impl == 0 && !conv && geglu && p.K == 320 && p.splitk <= 1 && ws_mode < 2 &&
+                          xl_supported(p, false, 256) && (long)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 1024;
+    // THE weight-stationary decision: the rowstat_out branch, the fused-LayerNorm branch and the launch below all read ws_taken (a K = 320 GEMM
+    // is never claimed by the forced-XL block further down unless XL_K320 is set, and then ws_taken is false).
+    const bool ws_first = !conv && ws_mode > 0 && p.splitk <= 1 && ws_supported(p) && (ws_mode >= 2 || p.M >= 8192);
+    const bool ws_taken = impl == 0 && !geglu_xl && ws_first && !(xl_k320 && xl_mode > 0);
+    if (p.rowstat) {
+        // Row statistics of C for the LayerNorm that reads it next (MdxGemmDesc.rowstat_out): the K = 320 weight-stationary kernel emits them
+        // from its store phase; every other route gets them from a small kernel over the finished C (part 0 = whole rows, the rest zeros).
+        // Past this block only launch_gemm_ws may see p.rowstat: the other launchers refuse it.
+        if (conv || p.batch > 1 || p.epi != 0 || p.c_f32 || p.Vt || p.rowstat_parts < 1) return set_error(MDX_EINVAL, "rowstat_out: plain 2-D GEMM with 16-bit C only");
+        if (!(ws_taken && ws_emits_rowstat(p) && opt(OPT_LN_FUSE))) {
+            GCParams q = p;
+            q.rowstat = nullptr; q.rowstat_parts = 0;
+            if (int rc = launch_gemm_conv(q, conv, st)) return rc;
+            return launch_rowstat((const bf16_t*)p.C, p.M, p.N, p.ldc, p.rowstat, p.rowstat_parts, st);
+        }
+    }
     // Width choice: time model fitted on MI355X at 384 views (profiles/README.md, round 2): a tile costs a(bn) + b(bn) * K/64
     // microseconds — b falls with the tile width (operand bytes per MAC through the global -> LDS path), a (prologue + the
     // HBM-bound epilogue burst; the 320-wide tile stages C in two halves) rises — times the rounds of tiles over the 256 CUs.
@@ -459,14 +468,6 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
         }
         return bn_out != 0;
     };
-    // K = 320 GEGLU with many rows: gemm_ws.hip (384 views: 1642 us) vs the 256 x 256 XL tile (1694-1757 us).  Before the ring of
-    // gemm_ws.hip really ran ahead (its DMA builtin drained the VM counter every slab: 1994 us) the XL tile was the faster one;
-    // MDX_XL_GEGLU320=1 selects it again.
-    const int xl_geglu320 = (int)opt(OPT_XL_GEGLU320);
-    const bool geglu_xl = xl_geglu320 && xl_mode == 1 && impl == 0 && !conv && geglu && p.K == 320 && p.splitk <= 1 && ws_mode < 2 &&
-                          xl_supported(p, false, 256) && (long)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 1024;
-    const bool ws_first = !conv && ws_mode > 0 && p.splitk <= 1 && ws_supported(p) && (ws_mode >= 2 || p.M >= 8192);
-    const bool ws_taken = impl == 0 && !geglu_xl && ws_first && !(xl_k320 && xl_mode > 0);
     if (p.ln_eps > 0.f) {
         // LayerNorm fused into this GEMM (MdxGemmDesc.ln_eps): the weight-stationary kernel normalises in-kernel; every other route gets
         // the rows normalised (no affine part: it is in W / bias) into the caller's scratch first.
@@ -575,14 +576,32 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
 
 using namespace mdx;
 
-static int check_common(int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, const void* A, const void* W,
-                        const void* C, int64_t N) {
-    if (K % 8) return set_error(MDX_EINVAL, "K=%ld must be a multiple of 8", (long)K);
-    if ((lda % 8) || (ldw % 8)) return set_error(MDX_EINVAL, "lda/ldw must be multiples of 8");
-    if ((ldc % 4) || (ldr % 4)) return set_error(MDX_EINVAL, "ldc/ldr must be multiples of 4");
-    if (((uintptr_t)A & 15) || ((uintptr_t)W & 15) || ((uintptr_t)C & 7))
-        return set_error(MDX_EINVAL, "operand pointers must be 16-byte (A, W) / 8-byte (C) aligned");
-    (void)N;
+static int check_common(const char* op, int64_t K, int64_t lda, int64_t ldw, int64_t ldc, int64_t ldr, const void* A, const void* W,
+                        const void* C, const char* nA, const char* nW, const char* nC, const char* nlda, const char* nldc) {
+    MDX_NEED(need_multiple(op, "K", K, 8));
+    MDX_NEED(need_multiple(op, nlda, lda, 8));
+    MDX_NEED(need_multiple(op, "ldw", ldw, 8));
+    MDX_NEED(need_multiple(op, nldc, ldc, 4));
+    MDX_NEED(need_multiple(op, "ldr", ldr, 4));
+    MDX_NEED(need_aligned(op, nA, A, 16));
+    MDX_NEED(need_aligned(op, nW, W, 16));
+    MDX_NEED(need_aligned(op, nC, C, 8));
+    return MDX_OK;
+}
+
+// The epilogue's side operands (include/mdx.h, "Requirements" of mdx_gemm_bf16 / mdx_conv2d_bf16): bias and the temb row are read as float4 by
+// every main loop, the split-K slabs as float4, a 16-bit residual as 8-byte pieces on the narrow path (16-byte ones only behind GCParams.wide).
+static int check_epilogue_operands(const char* op, const void* R, const float* bias, const float* temb, const int32_t* sel, const float* ws,
+                                   int64_t temb_sel_stride, int64_t temb_b_stride) {
+    MDX_NEED(need_aligned(op, "R", R, 8));
+    MDX_NEED(need_aligned(op, "bias", bias, 16));
+    MDX_NEED(need_aligned(op, "temb", temb, 16));
+    MDX_NEED(need_aligned(op, "sel_ptr", sel, 4));
+    MDX_NEED(need_aligned(op, "ws", ws, 16));
+    if (temb) {
+        MDX_NEED(need_multiple(op, "temb_sel_stride", temb_sel_stride, 4));
+        MDX_NEED(need_multiple(op, "temb_b_stride", temb_b_stride, 4));
+    }
     return MDX_OK;
 }
 
@@ -606,8 +625,20 @@ static int launch_gemm_flat(const mdx::GCParams& q, hipStream_t st) {
 
 extern "C" int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream) {
     if (!d || !d->A || !d->W || !d->C) return set_error(MDX_EINVAL, "mdx_gemm_bf16: null operand");
-    int rc = check_common(d->K, d->lda, d->ldw, d->ldc, d->ldr, d->A, d->W, d->C, d->N);
-    if (rc) return rc;
+    const char* op = "mdx_gemm_bf16";
+    MDX_NEED(need_int(op, "M", d->M)); MDX_NEED(need_int(op, "N", d->N)); MDX_NEED(need_int(op, "K", d->K));
+    MDX_NEED(need_int(op, "batch", d->batch)); MDX_NEED(need_int(op, "rows_per_b", d->rows_per_b));
+    MDX_NEED(need_int(op, "splitk", d->splitk));
+    MDX_NEED(check_common(op, d->K, d->lda, d->ldw, d->ldc, d->ldr, d->A, d->W, d->C, "A", "W", "C", "lda", "ldc"));
+    MDX_NEED(check_epilogue_operands(op, d->R, d->bias, d->temb, d->sel_ptr, d->ws, d->temb_sel_stride, d->temb_b_stride));
+    if (d->c_is_f32) {   // fp32 C / R move as float4 (epilogue_store, splitk_reduce_kernel)
+        MDX_NEED(need_aligned(op, "C (fp32)", d->C, 16));
+        MDX_NEED(need_aligned(op, "R (fp32)", d->R, 16));
+    }
+    if (d->batch > 1) {
+        MDX_NEED(need_multiple(op, "sA", d->sA, 8)); MDX_NEED(need_multiple(op, "sW", d->sW, 8));
+        MDX_NEED(need_multiple(op, "sC", d->sC, 4)); MDX_NEED(need_multiple(op, "sR", d->sR, 4));
+    }
     if (d->N % 4) {
         // ragged N (V^T with Tk % 4 != 0): columns N..roundup4(N)-1 are written as exact zeros
         // (their W rows are zero-filled), so they must exist in the row pitch and carry no epilogue.
@@ -676,9 +707,19 @@ extern "C" int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream) {
 extern "C" int mdx_conv2d_bf16(const MdxConvDesc* d, void* stream) {
     if (!d || !d->X || !d->Wt || !d->Y) return set_error(MDX_EINVAL, "mdx_conv2d_bf16: null operand");
     if (d->Cin % 8) return set_error(MDX_EINVAL, "mdx_conv2d_bf16: Cin=%ld must be a multiple of 8", (long)d->Cin);
+    const char* op = "mdx_conv2d_bf16";
+    MDX_NEED(need_int(op, "B", d->B)); MDX_NEED(need_int(op, "Hi", d->Hi)); MDX_NEED(need_int(op, "Wi", d->Wi)); MDX_NEED(need_int(op, "Cin", d->Cin));
+    MDX_NEED(need_int(op, "Ho", d->Ho)); MDX_NEED(need_int(op, "Wo", d->Wo)); MDX_NEED(need_int(op, "Cout", d->Cout));
+    MDX_NEED(need_int(op, "kh", d->kh)); MDX_NEED(need_int(op, "kw", d->kw)); MDX_NEED(need_int(op, "sh", d->sh)); MDX_NEED(need_int(op, "sw", d->sw));
+    MDX_NEED(need_int(op, "ph", d->ph)); MDX_NEED(need_int(op, "pw", d->pw)); MDX_NEED(need_int(op, "splitk", d->splitk));
+    if (d->B < 0 || d->Ho < 0 || d->Wo < 0 || d->kh < 0 || d->kw < 0 || d->Cin < 0) return set_error(MDX_EINVAL, "%s: negative size", op);
+    MDX_NEED(need_int(op, "Ho * Wo", d->Ho * d->Wo));
+    MDX_NEED(need_int(op, "B * Ho * Wo", d->B * (d->Ho * d->Wo)));
+    MDX_NEED(need_int(op, "kh * kw", d->kh * d->kw));
     int64_t K = d->kh * d->kw * d->Cin;
-    int rc = check_common(K, d->ldx, K, d->ldy, d->ldr, d->X, d->Wt, d->Y, d->Cout);
-    if (rc) return rc;
+    MDX_NEED(need_int(op, "kh * kw * Cin", K));
+    MDX_NEED(check_common(op, K, d->ldx, K, d->ldy, d->ldr, d->X, d->Wt, d->Y, "X", "Wt", "Y", "ldx", "ldy"));
+    MDX_NEED(check_epilogue_operands(op, d->R, d->bias, d->temb, d->sel_ptr, d->ws, d->temb_sel_stride, d->temb_b_stride));
     if (d->epilogue == MDX_EPI_GEGLU) return set_error(MDX_EINVAL, "conv has no GEGLU epilogue");
     if (d->Cout % 4) return set_error(MDX_EINVAL, "mdx_conv2d_bf16: Cout=%ld must be a multiple of 4", (long)d->Cout);
     GCParams p = {};

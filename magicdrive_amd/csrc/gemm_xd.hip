@@ -503,6 +503,8 @@ bool xd_supported(const GCParams& q) {
 }
 
 int launch_gemm_xd(const GCParams& q0, int cus, hipStream_t st) {
+    // (today's only caller, launch_xl, sits behind launch_gemm_xl's identical refusal: this one is for a caller that does not)
+    if (q0.rowstat) return set_error(MDX_EINVAL, "gemm_xd: rowstat_out reached a route that does not emit row statistics");
     GCParams q = q0;
 #ifdef XD_TIMING
     q.timing = (q0.ws && q0.ws_bytes >= (long)cus * 64) ? (unsigned long long*)q0.ws : nullptr;

@@ -1426,6 +1426,7 @@ bool xl_supported(const GCParams& p, bool conv, int bn) {
 // issued between the MFMAs (measured 10 % slower: the DMA issue lengthens the MFMA segments, which are the serial resource);
 // 2 / 3 = quadrant variants (see the kernel).
 int launch_gemm_xl(const GCParams& p, bool conv, int bn, hipStream_t st) {
+    if (p.rowstat) return set_error(MDX_EINVAL, "gemm_xl: rowstat_out reached a route that does not emit row statistics");
     const int sched = (int)opt(OPT_XL_SCHED);
 #define XL_GO(BN_, S_) (conv ? launch_xl<BN_, true, S_>(p, st) : launch_xl<BN_, false, S_>(p, st))
     if (bn == 320) {

@@ -43,6 +43,22 @@ inline int set_error(int code, const char* fmt, ...) {
     return code;
 }
 
+// Descriptor contract checks (include/mdx.h lists them per entry point): every entry point runs them before its first launch or
+// memset, so a descriptor a kernel cannot take never reaches the device.  The message names the field.
+inline int need_aligned(const char* op, const char* field, const void* ptr, unsigned bytes) {
+    if (((uintptr_t)ptr & (bytes - 1)) == 0) return MDX_OK;
+    return set_error(MDX_EINVAL, "%s: %s must be %u-byte aligned", op, field, bytes);
+}
+inline int need_multiple(const char* op, const char* field, int64_t v, int m) {
+    if (v % m == 0) return MDX_OK;
+    return set_error(MDX_EINVAL, "%s: %s=%ld must be a multiple of %d", op, field, (long)v, m);
+}
+inline int need_int(const char* op, const char* field, int64_t v) {       // a field the kernels hold in a 32-bit int
+    if (v <= 0x7fffffffL && v >= -0x7fffffffL) return MDX_OK;
+    return set_error(MDX_EINVAL, "%s: %s=%ld does not fit a 32-bit int", op, field, (long)v);
+}
+#define MDX_NEED(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+
 // Launch errors (bad configuration) surface through hipGetLastError without a sync.
 // `primary` = the kernel that does the op's work (reduce / finalise helpers pass false and keep the previous tag).
 inline int check_launch(const char* what, bool primary = true) {

@@ -448,8 +448,13 @@ using namespace mdx;
 extern "C" int mdx_groupnorm_bf16(const MdxGroupNormDesc* d, void* stream) {
     if (!d || !d->X || !d->Y || !d->gamma || !d->beta) return set_error(MDX_EINVAL, "mdx_groupnorm_bf16: null operand");
     if (d->G <= 0 || d->C % d->G) return set_error(MDX_EINVAL, "groupnorm: C=%ld not divisible by G=%ld", (long)d->C, (long)d->G);
+    const char* op = "mdx_groupnorm_bf16";
+    MDX_NEED(need_int(op, "B", d->B)); MDX_NEED(need_int(op, "HW", d->HW)); MDX_NEED(need_int(op, "C", d->C)); MDX_NEED(need_int(op, "G", d->G));
+    // the two-stage kernels read gamma / beta as float4 and keep their partials as fp32 triples; X / Y are served at any 2-byte alignment
+    MDX_NEED(need_aligned(op, "gamma", d->gamma, 16)); MDX_NEED(need_aligned(op, "beta", d->beta, 16)); MDX_NEED(need_aligned(op, "ws", d->ws, 16));
+    MDX_NEED(need_aligned(op, "X", d->X, 2)); MDX_NEED(need_aligned(op, "Y", d->Y, 2));
+    if (d->C <= 0 || d->ldx < d->C || d->ldy < d->C) return set_error(MDX_EINVAL, "%s: need 0 < C <= ldx, ldy", op);
     if (d->B <= 0 || d->HW <= 0) return MDX_OK;
-    if (d->C / d->G > GN_MAX_CPG) return set_error(MDX_EUNSUPPORTED, "groupnorm: %ld channels per group (at most %d)", (long)(d->C / d->G), GN_MAX_CPG);
     GNParams p;
     p.X = (const bf16_t*)d->X; p.Y = (bf16_t*)d->Y; p.gamma = d->gamma; p.beta = d->beta;
     p.B = (int)d->B; p.HW = (int)d->HW; p.C = (int)d->C; p.G = (int)d->G; p.ldx = d->ldx; p.ldy = d->ldy;
@@ -508,6 +513,8 @@ extern "C" int mdx_groupnorm_bf16(const MdxGroupNormDesc* d, void* stream) {
             return check_launch("gn_stats_kernel+gn_apply_kernel");
         }
     }
+    // the one-launch kernel keeps a group's gamma / beta in LDS: GN_MAX_CPG channels per group (a larger group is served above, or not at all)
+    if (cpg > GN_MAX_CPG) return set_error(MDX_EUNSUPPORTED, "groupnorm: %d channels per group (at most %d outside the two-stage path)", cpg, GN_MAX_CPG);
     // vector width limited by cpg and by the alignment of every group start / row stride
     int vec = 1;
     for (int v = 8; v > 1; v >>= 1) {
@@ -549,6 +556,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(SMParams p) {
 extern "C" int mdx_softmax_rows(const MdxSoftmaxDesc* d, void* stream) {
     if (!d || !d->X || !d->Y) return set_error(MDX_EINVAL, "mdx_softmax_rows: null operand");
     if (d->T <= 0 || d->ldx < d->T || d->ldy < d->T) return set_error(MDX_EINVAL, "softmax: need 0 < T <= ldx, ldy");
+    MDX_NEED(need_int("mdx_softmax_rows", "T", d->T)); MDX_NEED(need_int("mdx_softmax_rows", "ldy", d->ldy)); MDX_NEED(need_int("mdx_softmax_rows", "rows", d->rows));
+    MDX_NEED(need_aligned("mdx_softmax_rows", "X", d->X, 4)); MDX_NEED(need_aligned("mdx_softmax_rows", "Y", d->Y, 2));
     if (d->rows <= 0) return MDX_OK;
     mdx::SMParams p{d->X, (bf16_t*)d->Y, d->rows, (int)d->T, d->ldx, d->ldy, (float)d->scale};
     hipLaunchKernelGGL(mdx::softmax_rows_kernel, dim3((unsigned)((d->rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, p);
@@ -609,8 +618,12 @@ int launch_rowstat(const bf16_t* X, int M, int C, long ldx, float* stat, int par
 
 extern "C" int mdx_layernorm_bf16(const MdxLayerNormDesc* d, void* stream) {
     if (!d || !d->X || !d->Y || !d->gamma || !d->beta) return set_error(MDX_EINVAL, "mdx_layernorm_bf16: null operand");
-    if (d->C % 8 || d->ldx % 8 || d->ldy % 8) return set_error(MDX_EINVAL, "layernorm: C, ldx, ldy must be multiples of 8");
-    if (((uintptr_t)d->X & 15) || ((uintptr_t)d->Y & 15)) return set_error(MDX_EINVAL, "layernorm: 16-byte alignment required");
+    const char* op = "mdx_layernorm_bf16";
+    MDX_NEED(need_multiple(op, "C", d->C, 8)); MDX_NEED(need_multiple(op, "ldx", d->ldx, 8)); MDX_NEED(need_multiple(op, "ldy", d->ldy, 8));
+    MDX_NEED(need_aligned(op, "X", d->X, 16)); MDX_NEED(need_aligned(op, "Y", d->Y, 16));
+    MDX_NEED(need_aligned(op, "gamma", d->gamma, 16)); MDX_NEED(need_aligned(op, "beta", d->beta, 16));     // read as float4
+    MDX_NEED(need_int(op, "M", d->M));
+    if (d->C <= 0 || d->ldx < d->C || d->ldy < d->C) return set_error(MDX_EINVAL, "%s: need 0 < C <= ldx, ldy", op);
     if (d->C > 8 * 64 * 4) return set_error(MDX_EUNSUPPORTED, "layernorm: C=%ld > 2048", (long)d->C);
     if (d->M <= 0) return MDX_OK;
     LNParams p;
