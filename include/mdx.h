@@ -42,7 +42,7 @@ extern "C" {
 #define MDX_ELAUNCH (-2)     /* hip launch / runtime error */
 #define MDX_EUNSUPPORTED (-3)
 
-#define MDX_ABI_VERSION 10
+#define MDX_ABI_VERSION 11
 
 /* ---- epilogue flags shared by GEMM / conv ------------------------------- */
 #define MDX_EPI_NONE 0
@@ -156,7 +156,19 @@ typedef struct MdxConvDesc {
     int64_t ldx, ldy, ldr;
     int64_t temb_sel_stride, temb_b_stride;
     int64_t epilogue, splitk;
-    int64_t ws_bytes, reserved1;
+    int64_t ws_bytes;
+    /* ABI 11 (the field was reserved1): 1 = "upsampled 2x" mode — Y = conv3x3_pad1(nearest_resize(X, Ho x Wo)) computed from the LOW-RES X
+     * [B,Hi,Wi,Cin] without the resized tensor.  In the resized image every 2 x 2 block holds one pixel of X, so an output pixel's nine taps
+     * read four pixels of X: per output parity ("phase") the 3x3 filter folds into a 2x2 one.  Per axis the output indices fall in classes
+     *     0  even  o = 2 j      taps (j - 1, j)   weights (w0, w1 + w2)
+     *     1  odd   o = 2 j + 1  taps (j, j + 1)   weights (w0 + w1, w2)
+     *     2  the last even index when n_out = 2 n_in - 1 (its +1 tap is the conv's zero padding): taps (j - 1, j), weights (w0, w1)
+     * with 2 classes on an exact-2x axis and 3 on a cropped one (classes 0 / 1 then stop one index earlier).
+     * Wt = [ny * nx][Cout][2][2][Cin], set yc * nx + xc = the outer combination of the axis classes (magicdrive_amd/packing.py:
+     * fold_upsample_conv); kh = kw = 2 describe one set, sh = sw = 1, ph / pw are ignored.
+     * Needs Cin % 64 == 0, Ho in {2 Hi, 2 Hi - 1}, Wo in {2 Wi, 2 Wi - 1}, Hi * Wi + 256 < 2^24, on a cropped axis the whole extent of X (B * Hi * Wi * ldx * 2 bytes) below 2^31, and a bias-only epilogue (no R / temb /
+     * activation / split-K): anything else is MDX_EINVAL — the mode has one route (csrc/gemm_xl.hip) and no fallback.  0 = ordinary conv. */
+    int64_t upsample2x;
 } MdxConvDesc;
 int mdx_conv2d_bf16(const MdxConvDesc* d, void* stream);
 

@@ -414,6 +414,22 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
         p.wide = wide_on && !p.c_f32 && (nout % 8) == 0 && (p.ldc % 8) == 0 && (p.sC % 8) == 0 && (((uintptr_t)p.C) & 15) == 0 &&
                  (!p.R || ((p.ldr % 8) == 0 && (p.sR % 8) == 0 && (((uintptr_t)p.R) & 15) == 0));
     }
+    if (p.up2) {
+        // upsampled-2x conv (MdxConvDesc.upsample2x): only the XL main loop knows the mode; the width by the same time model as try_xl below
+        if (!conv) return set_error(MDX_EINVAL, "upsample2x: conv only");
+        int bn_up = 0; double best = 1e300;
+        const int mt = up_mtiles(p);
+        for (int bn : {320, 256}) {
+            if (!xl_supported(p, true, bn)) continue;
+            const long t = (long)mt * ((p.N + bn - 1) / bn);
+            const double a = bn == 320 ? 23.7 : 13.4, b = bn == 320 ? 1.896 : 1.565;
+            const double c = (double)((t + 255) / 256) * (a + b * p.K / 64.0);
+            if (c < best) { best = c; bn_up = bn; }
+        }
+        if (const int xl_bn = (int)opt(OPT_XL_BN)) if ((xl_bn == 320 || xl_bn == 256) && xl_supported(p, true, xl_bn)) bn_up = xl_bn;
+        if (!bn_up) return set_error(MDX_EINVAL, "mdx_conv2d: upsample2x needs Cin %% 64 == 0, Ho in {2 Hi, 2 Hi - 1}, Wo in {2 Wi, 2 Wi - 1}, bias-only epilogue, no split-K; with a cropped axis B * Hi * Wi * ldx * 2 < 2^31");
+        return launch_gemm_xl(p, true, bn_up, st);
+    }
     if (!opt(OPT_LN_STATS)) { p.rowstat = nullptr; p.rowstat_parts = 0; p.ln_stats = nullptr; p.ln_stats_parts = 0; }   // A/B: the round-5 data flow
     if (geglu && (p.N % 64) != 0) return set_error(MDX_EINVAL, "GEGLU needs packed N %% 64 == 0 (N=%d)", p.N);
     constexpr int impl = 0;
@@ -718,6 +734,13 @@ extern "C" int mdx_conv2d_bf16(const MdxConvDesc* d, void* stream) {
     MDX_NEED(need_int(op, "kh * kw", d->kh * d->kw));
     int64_t K = d->kh * d->kw * d->Cin;
     MDX_NEED(need_int(op, "kh * kw * Cin", K));
+    if (d->upsample2x != 0 && d->upsample2x != 1) return set_error(MDX_EINVAL, "%s: upsample2x=%ld must be 0 or 1", op, (long)d->upsample2x);
+    if (d->upsample2x) {
+        if (d->kh != 2 || d->kw != 2 || d->sh != 1 || d->sw != 1 || d->R || d->temb || d->epilogue || d->splitk > 1 || d->B < 1 || d->Hi < 1 || d->Wi < 1 ||
+            (d->Ho != 2 * d->Hi && d->Ho != 2 * d->Hi - 1) || (d->Wo != 2 * d->Wi && d->Wo != 2 * d->Wi - 1))
+            return set_error(MDX_EINVAL, "%s: upsample2x needs kh = kw = 2 (phase weights), stride 1, Ho in {2 Hi, 2 Hi - 1}, Wo in {2 Wi, 2 Wi - 1}, "
+                                         "no residual / temb / activation / split-K", op);
+    }
     MDX_NEED(check_common(op, K, d->ldx, K, d->ldy, d->ldr, d->X, d->Wt, d->Y, "X", "Wt", "Y", "ldx", "ldy"));
     MDX_NEED(check_epilogue_operands(op, d->R, d->bias, d->temb, d->sel_ptr, d->ws, d->temb_sel_stride, d->temb_b_stride));
     if (d->epilogue == MDX_EPI_GEGLU) return set_error(MDX_EINVAL, "conv has no GEGLU epilogue");
@@ -735,5 +758,6 @@ extern "C" int mdx_conv2d_bf16(const MdxConvDesc* d, void* stream) {
     p.kh = (int)d->kh; p.kw = (int)d->kw; p.sh = (int)d->sh; p.sw = (int)d->sw; p.ph = (int)d->ph; p.pw = (int)d->pw;
     const int cim = (int)opt(OPT_CONV_CIMAJOR);
     p.cimajor = (cim && d->kh * d->kw > 1 && d->Cin % 64 == 0) ? 1 : 0;
+    if (d->upsample2x) { p.up2 = 1; p.upB = (int)d->B; p.splitk = 1; }
     return launch_gemm_conv(p, true, (hipStream_t)stream);
 }

@@ -49,9 +49,21 @@ __device__ __forceinline__ bool xl_tile_coords_at(const GCParams& p, int bid, in
 }
 __device__ __forceinline__ bool xl_tile_coords(const GCParams& p, int& tm, int& tn) { return xl_tile_coords_at(p, (int)blockIdx.x, tm, tn); }
 
-template <int BN, bool CONV, int SCHED>
+// q = n / d for 0 <= n < 2^24 from the fp32 reciprocal rd = 1 / d: the estimate is off by at most one, fixed by the remainder's sign
+__device__ __forceinline__ int xl_div24(int n, int d, float rd) {
+    const int q = (int)((float)n * rd);
+    const int r = n - q * d;
+    return r < 0 ? q - 1 : r >= d ? q + 1 : q;
+}
+
+// TAPS: K slabs per 64-channel block of a conv: 9 = the 3x3 / pad 1 conv; 4 = one 2x2 phase conv of the upsampled-2x mode (the tile index selects
+// the phase: its weight set, its padding and the strided rows of Y it stores).
+template <int BN, bool CONV, int SCHED, int TAPS = 9>
 __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     using G = Geo<BN>;
+    constexpr bool UP = CONV && TAPS == 4;
+    constexpr int KW = UP ? 2 : 3;
+    static_assert(TAPS == 9 || (TAPS == 4 && CONV && SCHED == 0), "tap counts: 9 (3x3) or 4 (2x2 phase of the upsampled-2x conv)");
     constexpr int BM = 256, NTH = 512;
     constexpr int TI = G::TI, TJ = G::TJ, TJ0 = G::TJ0, TJ1 = TJ - TJ0, TIH = TI / 2;
     constexpr int A_BYTES = BM * 128, B_BYTES = G::BNP * 128, BUF = A_BYTES + B_BYTES;
@@ -85,6 +97,27 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     unsigned long long ts_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define XL_STAMP(k) if (p.timing) ts_[k] = __builtin_amdgcn_s_memtime();
     XL_STAMP(0)
+    // rows of the problem this tile belongs to, input row / column of output pixel (0, 0)'s first tap and the stride (3x3: the conv's own)
+    int M_ = p.M, y_org = -p.ph, x_org = -p.pw, sh_ = p.sh, sw_ = p.sw;
+    int up_Hp = 1, up_Wp = 1, up_oy0 = 0, up_ox0 = 0;            // UP: the phase's grid and the output pixel of its (0, 0)
+    const bf16_t* Wb = p.W;
+    if constexpr (UP) {
+        const int nx = 2 + (p.Wo != 2 * p.Wi), nph = (2 + (p.Ho != 2 * p.Hi)) * nx;
+        for (int ph = 0; ph < nph; ++ph) {
+            const int yc = ph / nx, xc = ph - yc * nx;
+            const UpAxis ay = up_axis(yc, p.Hi, p.Ho), ax = up_axis(xc, p.Wi, p.Wo);
+            const int rows = p.upB * ay.cnt * ax.cnt, mtp = (rows + 255) / 256;
+            if (tile_m < mtp || ph == nph - 1) {
+                M_ = rows; up_Hp = ay.cnt; up_Wp = ax.cnt;
+                y_org = ay.first - ay.pad; x_org = ax.first - ax.pad;
+                up_oy0 = 2 * ay.first + ay.par; up_ox0 = 2 * ax.first + ax.par;
+                Wb = p.W + (long)ph * p.N * p.ldw;
+                break;
+            }
+            tile_m -= mtp;
+        }
+        sh_ = 1; sw_ = 1;
+    }
     const int m0 = tile_m * BM, n0 = tile_n * BN;
     const int nt = p.K / 64;                                    // K % 64 == 0 (xl_supported)
 
@@ -93,16 +126,18 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     // pixel, voffset = (input pixel of the row's tap (0,0)) - that, soffset = tap shift + channel block; invalid taps -> XL_OOB.
     long a_base_el;                                              // element offset of the descriptor base inside p.A
     int hw = 1, Wo = 1;
+    int tile_b0 = 0, tile_r0 = 0;                                // image / pixel inside it of the tile's first row
     if (CONV) {
-        hw = p.Ho * p.Wo; Wo = p.Wo;
+        hw = UP ? up_Hp * up_Wp : p.Ho * p.Wo; Wo = UP ? up_Wp : p.Wo;
         const int b = m0 / hw, rem = m0 - b * hw;
+        tile_b0 = b; tile_r0 = rem;
         const int oy = rem / Wo, ox = rem - oy * Wo;
-        a_base_el = (((long)b * p.Hi + (oy * p.sh - p.ph)) * p.Wi + (ox * p.sw - p.pw)) * p.lda;   // may point before p.A: never dereferenced there
+        a_base_el = (((long)b * p.Hi + (oy * sh_ + y_org)) * p.Wi + (ox * sw_ + x_org)) * p.lda;   // may point before p.A: never dereferenced there
     } else {
         a_base_el = (long)m0 * p.lda;
     }
     const xl_rsrc_t rsA = xl_make_rsrc(p.A + a_base_el);
-    const xl_rsrc_t rsB = xl_make_rsrc(p.W + (long)n0 * p.ldw);
+    const xl_rsrc_t rsB = xl_make_rsrc(Wb + (long)n0 * p.ldw);
     const unsigned lds0 = (unsigned)(unsigned long long)(lds_void_t*)smem;      // LDS byte address of the dynamic region
 
     // SCHED 4 keeps its per-lane state in TWO registers (the 320-wide kernel has none to spare: 160 accumulators + 56 fragment registers):
@@ -139,21 +174,21 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                 xs_bits |= bits << (3 * (2 * h + e));             // (a_voff / a_taps stay unused: ONE base offset + the piece's wave-uniform row offset, XS_PIECE_A)
             } else
             if (CONV) {
-                const int mm = min(m, p.M - 1);
+                const int mm = min(m, M_ - 1);
                 const int b = mm / hw, rem = mm - b * hw;
                 const int oy = rem / Wo, ox = rem - oy * Wo;
-                const int iy0 = oy * p.sh - p.ph, ix0 = ox * p.sw - p.pw;
+                const int iy0 = oy * sh_ + y_org, ix0 = ox * sw_ + x_org;
                 const long pix = ((long)b * p.Hi + iy0) * p.Wi + ix0;
                 a_voff[h][e] = (unsigned)((pix * p.lda - a_base_el) * 2 + cl * 16);
                 unsigned bits = 0;
 #pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int iy = iy0 + t / 3, ix = ix0 + t % 3;
-                    if (m < p.M && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi) bits |= 1u << t;
+                for (int t = 0; t < TAPS; ++t) {
+                    const int iy = iy0 + t / KW, ix = ix0 + t % KW;
+                    if (m < M_ && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi) bits |= 1u << t;
                 }
                 a_taps[h][e] = bits;
             } else {
-                a_voff[h][e] = m < p.M ? (unsigned)(((long)R * p.lda) * 2 + cl * 16) : XL_OOB;
+                a_voff[h][e] = m < M_ ? (unsigned)(((long)R * p.lda) * 2 + cl * 16) : XL_OOB;
             }
         }
     unsigned b_voff[2][UNIT_MAX];
@@ -188,9 +223,9 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     const int row_bytes = (int)(p.lda * 2);
     auto a_soff = [&](int T, int& tap) -> int {
         if (CONV) {
-            const int cb = T / 9;
-            tap = T - cb * 9;
-            const int ky = tap / 3, kx = tap - ky * 3;
+            const int cb = T / TAPS;
+            tap = T - cb * TAPS;
+            const int ky = tap / KW, kx = tap - ky * KW;
             return (ky * p.Wi + kx) * row_bytes + cb * 128;
         }
         tap = 0;
@@ -198,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     };
     auto b_soff = [&](int T) -> int {
         if (CONV) {
-            const int cb = T / 9, tap = T - cb * 9;
+            const int cb = T / TAPS, tap = T - cb * TAPS;
             return (tap * p.Cin + cb * 64) * 2;
         }
         return T * 128;
@@ -751,6 +786,19 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
 #else
     const bool rpref = Rg != nullptr && p.wide && !geglu;
 #endif
+    // element offset in C of row `rt` of this tile.  UP: row -> (image, low-res pixel of the phase's grid) -> the strided pixel of Y it owns
+    const float up_rhw = UP ? 1.0f / (float)hw : 0.f, up_rw = UP ? 1.0f / (float)Wo : 0.f;
+    auto c_off = [&](int rt) -> long {
+        if constexpr (UP) {
+            int r = tile_r0 + rt;                                 // < hw + 256 < 2^24 (xl_supported)
+            const int bb = xl_div24(r, hw, up_rhw);
+            r -= bb * hw;
+            const int j = xl_div24(r, Wo, up_rw), i = r - j * Wo;
+            return (((long)(tile_b0 + bb) * p.Ho + (up_oy0 + 2 * j)) * p.Wo + (up_ox0 + 2 * i)) * p.ldc;
+        } else {
+            return (long)(m0 + rt) * p.ldc;
+        }
+    };
     uint4 rpre[RIT];
     auto fetch_residual = [&](int hh) {
         const int mh_ = m0 + hh * HROWS;
@@ -951,7 +999,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                 for (int u = 0; u < 8; ++u) {
                     const int idx = i0 + u * NTH + tid;
                     const int row = idx / cpr, c8 = (idx - row * cpr) * 8;
-                    if (idx < total && mh + row < p.M && n0o + c8 < Nout) *(uint4*)(Cg + (long)(mh + row) * p.ldc + n0o + c8) = v[u];
+                    if (idx < total && mh + row < M_ && n0o + c8 < Nout) *(uint4*)(Cg + c_off(hh * HROWS + row) + n0o + c8) = v[u];
                 }
             }
         } else if (p.wide) {
@@ -967,7 +1015,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                     const int idx = i0 + u * NTH + tid;
                     row[u] = idx / cpr;
                     c8[u] = (idx - row[u] * cpr) * 8;
-                    ok[u] = idx < total && mh + row[u] < p.M && n0o + c8[u] < Nout;
+                    ok[u] = idx < total && mh + row[u] < M_ && n0o + c8[u] < Nout;
                     rv[u] = make_uint4(0, 0, 0, 0);
                     if (Rg && ok[u]) rv[u] = *(const uint4*)(Rg + (long)(mh + row[u]) * p.ldr + n0o + c8[u]);
                 }
@@ -976,7 +1024,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                     if (!ok[u]) continue;
                     uint4 v = *(const uint4*)(Cs + row[u] * CSTR + c8[u]);
                     if (Rg) { v.x = add2bf(v.x, rv[u].x); v.y = add2bf(v.y, rv[u].y); v.z = add2bf(v.z, rv[u].z); v.w = add2bf(v.w, rv[u].w); }
-                    *(uint4*)(Cg + (long)(mh + row[u]) * p.ldc + n0o + c8[u]) = v;
+                    *(uint4*)(Cg + c_off(hh * HROWS + row[u]) + n0o + c8[u]) = v;
                 }
             }
         } else {
@@ -992,7 +1040,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                     const int idx = i0 + u * NTH + tid;
                     row[u] = idx / cpr;
                     c4[u] = (idx - row[u] * cpr) * 4;
-                    ok[u] = idx < total && mh + row[u] < p.M && n0o + c4[u] < Nout;
+                    ok[u] = idx < total && mh + row[u] < M_ && n0o + c4[u] < Nout;
                     rv[u] = make_uint2(0, 0);
                     if (Rg && ok[u]) rv[u] = *(const uint2*)(Rg + (long)(mh + row[u]) * p.ldr + n0o + c4[u]);
                 }
@@ -1001,7 +1049,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
                     if (!ok[u]) continue;
                     uint2 v = *(const uint2*)(Cs + row[u] * CSTR + c4[u]);
                     if (Rg) { v.x = add2bf(v.x, rv[u].x); v.y = add2bf(v.y, rv[u].y); }
-                    *(uint2*)(Cg + (long)(mh + row[u]) * p.ldc + n0o + c4[u]) = v;
+                    *(uint2*)(Cg + c_off(hh * HROWS + row[u]) + n0o + c4[u]) = v;
                 }
             }
         }
@@ -1337,15 +1385,15 @@ constexpr size_t xl_smem_bytes() {
 bool xd_supported(const GCParams& q);                                          // gemm_xd.hip
 int launch_gemm_xd(const GCParams& q, int cus, hipStream_t st);
 
-template <int BN, bool CONV, int SCHED>
+template <int BN, bool CONV, int SCHED, int TAPS = 9>
 static int launch_xl(const GCParams& p, hipStream_t st) {
     constexpr size_t smem_kxs = (size_t)2 * 272 * 128 + (size_t)2 * Geo<BN>::BNP * 128;      // SCHED 4: two 272-row A buffers + two weight slabs
     constexpr size_t smem = (SCHED == 4 && smem_kxs > xl_smem_bytes<BN>()) ? smem_kxs : xl_smem_bytes<BN>();
     static_assert(smem <= 163840, "LDS budget");
-    auto kern = gemm_xl_kernel<BN, CONV, SCHED>;
+    auto kern = gemm_xl_kernel<BN, CONV, SCHED, TAPS>;
     if (int rc = ensure_dyn_smem((const void*)kern, smem, "xl")) return rc;
     GCParams q = p;
-    q.mt = (p.M + 255) / 256; q.nt = (p.N + BN - 1) / BN;
+    q.mt = TAPS == 4 ? up_mtiles(p) : (p.M + 255) / 256; q.nt = (p.N + BN - 1) / BN;
     const int swz = (int)opt(OPT_GEMM_SWZ);
     const int dbg = (int)opt(OPT_XL_DBG);
     q.dbg = dbg;
@@ -1394,7 +1442,7 @@ static int launch_xl(const GCParams& p, hipStream_t st) {
     }
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, st, q);
     char tag[96];
-    snprintf(tag, sizeof tag, "gemm_xl_kernel<256x%d,%s>", BN, CONV ? (SCHED == 4 ? "conv,kxs" : "conv") : "gemm");   // (schedules 0-3 are tuning knobs, not part of the name)
+    snprintf(tag, sizeof tag, "gemm_xl_kernel<256x%d,%s>", BN, CONV ? (SCHED == 4 ? "conv,kxs" : TAPS == 4 ? "conv,up2x" : "conv") : "gemm");   // (schedules 0-3 are tuning knobs, not part of the name)
     return check_launch(tag);
 }
 
@@ -1407,7 +1455,20 @@ bool xl_supported(const GCParams& p, bool conv, int bn) {
     // SiLU epilogue: only the prologue's map-encoder convs and the time MLP use it (never >= 160 tiles); instantiating it here cost the
     // 256-wide kernels 17 spilled VGPRs (the residual prefetch went through scratch behind a full vmcnt wait)
     if (p.epi == 2) return false;
-    if (conv) {
+    if (conv && p.up2) {
+        // upsampled-2x mode: 2x2 phase convs of the low-res input (bias only), 256- or 320-wide tiles; the epilogue's row map divides
+        // (pixel inside the image + 256) through fp32 reciprocals: exact below 2^24
+        // (the K order of the phase weights is the kernel's own: GCParams.cimajor does not apply)
+        if (bn == 160 || p.kh != 2 || p.kw != 2 || (p.Cin % 64) || p.R || p.temb || p.epi || p.col_split) return false;
+        if (p.upB < 1 || p.Hi < 1 || p.Wi < 1 || (p.Ho != 2 * p.Hi && p.Ho != 2 * p.Hi - 1) || (p.Wo != 2 * p.Wi && p.Wo != 2 * p.Wi - 1)) return false;
+        if ((long)p.Hi * p.Wi + 256 >= (1L << 24) || (long)p.upB * p.Hi * p.Wi >= 0x7fffff00L) return false;
+        const long span = ((long)(256 / p.Wi + 3) * p.Wi + 256L + 2 * p.Wi) * p.lda * 2;
+        if (span >= 0x40000000L) return false;
+        // a cropped axis adds edge classes whose grid is one row / column (or one pixel) per image: 256 tile rows then step through up to 256
+        // IMAGES, so the per-lane offsets are bounded only by the whole extent of X (+ the Wi + 1 pixels by which a pad-1 tile's base may lie
+        // before X), which must fit the descriptor's 2 GiB window
+        if ((p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi) && ((long)p.upB * p.Hi * p.Wi + p.Wi + 2) * p.lda * 2 >= 0x7fff0000L) return false;
+    } else if (conv) {
         if (p.kh != 3 || p.kw != 3 || p.ph != 1 || p.pw != 1 || (p.Cin % 64) || !p.cimajor) return false;   // pad 1: input pixel index monotonic in m
         // voffsets are relative to the tile's first receptive-field pixel: 256 output pixels span < 2^31 bytes for every real shape,
         // but keep the arithmetic honest
@@ -1428,6 +1489,10 @@ bool xl_supported(const GCParams& p, bool conv, int bn) {
 int launch_gemm_xl(const GCParams& p, bool conv, int bn, hipStream_t st) {
     if (p.rowstat) return set_error(MDX_EINVAL, "gemm_xl: rowstat_out reached a route that does not emit row statistics");
     const int sched = (int)opt(OPT_XL_SCHED);
+    if (p.up2) {
+        if (!conv || !xl_supported(p, true, bn)) return set_error(MDX_EINVAL, "gemm_xl: upsampled-2x conv on an unsupported shape");
+        return bn == 320 ? launch_xl<320, true, 0, 4>(p, st) : launch_xl<256, true, 0, 4>(p, st);
+    }
 #define XL_GO(BN_, S_) (conv ? launch_xl<BN_, true, S_>(p, st) : launch_xl<BN_, false, S_>(p, st))
     if (bn == 320) {
         // 3x3 / stride 1 convs: the three horizontal taps of a (channel block, ky) share one A slab (schedule 4; XL_KXSHARE = 0: per-tap slabs, A/B)

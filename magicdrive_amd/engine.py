@@ -60,6 +60,9 @@ class PackedNet:
     def conv(self, key):                               # [Cout,kh,kw,Cin] bf16
         return self._get("conv", [key], lambda w: PK.pack_conv_weight(w, self.dtype))
 
+    def conv_up2x(self, key, crop_h: bool, crop_w: bool):  # [phases,Cout,2,2,Cin]: the 3x3 filter folded over a 2x nearest resize, in fp32, rounded once
+        return self._get(("convup2x", bool(crop_h), bool(crop_w)), [key], lambda w: PK.fold_upsample_conv(w, crop_h, crop_w, self.dtype))
+
     def conv_cin_padded(self, key, cin_pad: int):      # [Cout,kh,kw,cin_pad] bf16, extra input channels zero
         def f(w):
             wp = torch.zeros(w.shape[0], cin_pad, w.shape[2], w.shape[3])
@@ -255,8 +258,25 @@ class ActSlice:
         return self.parent.btc[..., self.c0:self.c0 + self.C]
 
 
+def upsample_conv_folds(device, fold, Hi: int, Wi: int, Ho: int, Wo: int, cin: int, B: int = 0, ldx: int = 0) -> bool:
+    """Emit Upsample2D as ONE conv in the upsampled-2x mode?  `fold` None = on GPU devices only (CPU plans keep the resize + conv pair the
+    interpreter of the tests runs); True forces it wherever the mode can serve the shape.  The decision does not depend on the batch: a
+    1-scene call and a 64-scene call of the same model run the same (folded) weights, so the batch-consistency of the sampler compares
+    routes only.  The mode needs the nearest map to be o >> 1 on both
+    axes, Cin % 64 == 0 and, on a cropped axis, X within a 2 GiB window (MdxConvDesc.upsample2x); anything else keeps the pair."""
+    if fold is None:
+        fold = torch.device(device).type == "cuda"
+    if not (bool(fold) and cin % 64 == 0 and Hi * Wi + 256 < (1 << 24) and PK.upsample_fold_ok(Hi, Ho) and PK.upsample_fold_ok(Wi, Wo)):
+        return False
+    if B and (Ho != 2 * Hi or Wo != 2 * Wi) and (B * Hi * Wi + Wi + 2) * (ldx or cin) * 2 >= 0x7fff0000:
+        return False
+    return True
+
+
 class Builder:
     """Emits IR ops for the two networks at a fixed batch geometry."""
+
+    fold_upsample = None                  # Upsample2D as one upsampled-2x conv: None = on GPU devices, True / False = forced (upsample_conv_folds)
 
     def __init__(self, cfg, device, n_views: int, n_cam: int, ws_mb: int = 64, dtype=BF16):
         self.cfg = cfg
@@ -619,6 +639,16 @@ class Builder:
             uk = f"up_blocks.{i}.upsamplers.0.conv."
             if net.has(uk + "weight"):
                 Ho, Wo = skips[-1].H, skips[-1].W          # next skip's size (forced interpolation size)
+                if upsample_conv_folds(self.device, self.fold_upsample, x.H, x.W, Ho, Wo, x.C, B=x.B, ldx=x.bhwc.stride(2)):
+                    # the resize folded into the conv's weights: one launch on the low-res tensor, no `up` buffer (DESIGN.md "Upsample fold")
+                    cat = cats.pop(0) if placed else self.new(x.B, Ho, Wo, x.C + skips[-1].C)
+                    assert (cat.H, cat.W, cat.C) == (Ho, Wo, x.C + skips[-1].C)
+                    y = cat.channels(0, x.C)
+                    self.emit(O.Conv(x.bhwc, net.conv_up2x(uk + "weight", Ho != 2 * x.H, Wo != 2 * x.W), y.bhwc, bias=net.vec(uk + "bias"), ws=self.ws,
+                                     upsample2x=True, name=f"{tag}.u{i}.upconv"))
+                    self.free(x)
+                    x = y
+                    continue
                 up = self.new(x.B, Ho, Wo, x.C)
                 self.emit(O.Upsample(x.bhwc, up.bhwc, PK.nearest_index(x.H, Ho).to(self.device), PK.nearest_index(x.W, Wo).to(self.device), name=f"{tag}.u{i}.nearest"))
                 self.free(x)

@@ -36,6 +36,8 @@ def op_flops(op) -> float:
         return 2.0 * batch * M * N * K
     if isinstance(op, O.Conv):
         B, Ho, Wo, Cout = op.Y.shape
+        if getattr(op, "upsample2x", False):               # the algorithmic count of what it replaces: 9 taps at the output size (4 are executed)
+            return 2.0 * B * Ho * Wo * Cout * 9 * op.Wt.shape[-1]
         _, kh, kw, Cin = op.Wt.shape
         return 2.0 * B * Ho * Wo * Cout * kh * kw * Cin
     if isinstance(op, O.Attn):

@@ -162,7 +162,9 @@ class Gemm:
 
 @dataclass
 class Conv:
-    """Channels-last conv: X [B,Hi,Wi,Cin], Wt [Cout,kh,kw,Cin] packed bf16, Y [B,Ho,Wo,Cout]."""
+    """Channels-last conv: X [B,Hi,Wi,Cin], Wt [Cout,kh,kw,Cin] packed bf16, Y [B,Ho,Wo,Cout].
+    upsample2x: Y = conv3x3(pad 1)(nearest resize of X to Ho x Wo) from the low-res X; Wt = packing.fold_upsample_conv's
+    [phases,Cout,2,2,Cin] (MdxConvDesc.upsample2x)."""
     X: torch.Tensor
     Wt: torch.Tensor
     Y: torch.Tensor
@@ -182,12 +184,38 @@ class Conv:
     splitk: int = 0
     ws: Optional[torch.Tensor] = None
     name: str = ""
+    upsample2x: bool = False
 
     @property
     def opcode(self):
         return L.OP_CONV_DIRECT if self.direct else L.OP_CONV
 
+    def _lower_upsample2x(self):
+        B, Hi, Wi, Cin, ldx = _nhwc(self.X)
+        B2, Ho, Wo, Cout, ldy = _nhwc(self.Y)
+        _chk(self.Wt.dim() == 5 and self.Wt.is_contiguous() and self.Wt.dtype in H16, f"conv {self.name}: upsample2x takes packed phase weights")
+        nph, Co2, kh, kw, Ci2 = self.Wt.shape
+        _chk(B == B2 and Cout == Co2 and Cin == Ci2 and (kh, kw) == (2, 2), f"conv {self.name}: shape mismatch")
+        _chk(Ho in (2 * Hi, 2 * Hi - 1) and Wo in (2 * Wi, 2 * Wi - 1) and nph == (2 + (Ho != 2 * Hi)) * (2 + (Wo != 2 * Wi)), f"conv {self.name}: upsample2x sizes")
+        _chk(not self.direct and self.R is None and self.temb is None and self.epilogue == L.EPI_NONE and tuple(self.stride) == (1, 1),
+             f"conv {self.name}: upsample2x has a bias-only epilogue")
+        _chk(self.X.dtype == self.Wt.dtype and self.Y.dtype == self.Wt.dtype, f"conv {self.name}: the MFMA path takes one 16-bit type")
+        d = L.MdxConvDesc()
+        d.X, d.Wt, d.Y = _p(self.X), _p(self.Wt), _p(self.Y)
+        if self.bias is not None:
+            _chk(self.bias.dtype == F32 and self.bias.numel() == Cout, f"conv {self.name}: bias")
+            d.bias = _p(self.bias)
+        d.B, d.Hi, d.Wi, d.Cin, d.Ho, d.Wo, d.Cout = B, Hi, Wi, Cin, Ho, Wo, Cout
+        d.kh, d.kw, d.sh, d.sw, d.ph, d.pw = 2, 2, 1, 1, 0, 0
+        d.ldx, d.ldy = ldx, ldy
+        d.upsample2x = 1
+        if self.ws is not None:
+            d.ws = _p(self.ws); d.ws_bytes = self.ws.numel() * self.ws.element_size()
+        return self.opcode, d
+
     def lower(self):
+        if self.upsample2x:
+            return self._lower_upsample2x()
         B, Hi, Wi, Cin, ldx = _nhwc(self.X)
         B2, Ho, Wo, Cout, ldy = _nhwc(self.Y)
         Co2, kh, kw, Ci2 = self.Wt.shape

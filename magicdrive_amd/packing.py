@@ -5,6 +5,7 @@ Reference state-dict tensors (diffusers / MagicDrive layout) -> the layouts the 
   * GEGLU proj    [2F, K] (value rows | gate rows, attention.py:259-280) -> 32-row interleave so one
     MFMA wave tile holds a feature's value and gate in the same register slot
   * nearest-neighbour source indices for Upsample2D (resnet.py:154-163), torch's float32 rule
+  * Upsample2D's 3x3 conv folded over its 2x nearest resize: 2x2 phase filters on the low-res input (MdxConvDesc.upsample2x)
 """
 from __future__ import annotations
 
@@ -53,6 +54,62 @@ def nearest_index(n_in: int, n_out: int) -> torch.Tensor:
     dst = np.arange(n_out, dtype=np.float32)
     src = np.minimum(np.floor(dst * scale).astype(np.int64), n_in - 1)
     return torch.from_numpy(src.astype(np.int32))
+
+
+# ---- Upsample2D fold: conv3x3(pad 1) o nearest-2x  ==  four 2x2 phase convs of the low-res input (include/mdx.h: MdxConvDesc.upsample2x) ----
+# In the resized image pixel o reads source o >> 1, so along one axis the taps (o - 1, o, o + 1) of an output index read two sources:
+#   class 0  even o = 2 j       sources (j - 1, j)   weights (w0, w1 + w2)
+#   class 1  odd  o = 2 j + 1   sources (j, j + 1)   weights (w0 + w1, w2)
+#   class 2  the last even index when n_out = 2 n_in - 1: its +1 tap is the conv's zero padding, not source j -> (w0, w1)
+# An exact-2x axis has classes 0, 1; a cropped one 0, 1, 2 (0 and 1 then stop one source index earlier).
+
+def upsample_fold_ok(n_in: int, n_out: int) -> bool:
+    """The fold is valid where the nearest map is o >> 1 and the size is 2 n or 2 n - 1."""
+    return n_in >= 1 and n_out in (2 * n_in, 2 * n_in - 1) and bool(torch.equal(nearest_index(n_in, n_out), torch.arange(n_out, dtype=torch.int32) >> 1))
+
+
+def upsample_axis_classes(n_in: int, n_out: int):
+    """[(count, first source index, pad, parity)] per class of one axis: class c covers sources first .. first + count - 1 and writes
+    output index 2 j + parity; its two taps read sources j - pad, j - pad + 1."""
+    crop = int(n_out != 2 * n_in)
+    cls = [(n_in - crop, 0, 1, 0), (n_in - crop, 0, 0, 1)]
+    if crop:
+        cls.append((1, n_in - 1, 1, 0))
+    return cls
+
+
+def _fold_axis(w: torch.Tensor, dim: int, c: int) -> torch.Tensor:
+    w0, w1, w2 = w.unbind(dim)
+    pair = (w0, w1 + w2) if c == 0 else (w0 + w1, w2) if c == 1 else (w0, w1)
+    return torch.stack(pair, dim)
+
+
+def fold_upsample_conv(w: torch.Tensor, crop_h: bool, crop_w: bool, dtype=torch.bfloat16) -> torch.Tensor:
+    """3x3 filter [Cout, Cin, 3, 3] -> phase filters [ny * nx, Cout, 2, 2, Cin] (set yc * nx + xc), summed in the precision of `w`
+    (fp32 at pack time) and rounded ONCE to `dtype` (None: not rounded)."""
+    assert w.dim() == 4 and w.shape[2:] == (3, 3)
+    ny, nx = 2 + int(crop_h), 2 + int(crop_w)
+    sets = [_fold_axis(_fold_axis(w.detach(), 2, yc), 3, xc).permute(0, 2, 3, 1) for yc in range(ny) for xc in range(nx)]
+    out = torch.stack(sets, 0).contiguous()
+    return out if dtype is None else out.to(dtype)
+
+
+def folded_upsample_conv_reference(x: torch.Tensor, wf: torch.Tensor, Ho: int, Wo: int, bias=None) -> torch.Tensor:
+    """What the upsampled-2x conv computes, in torch: x [B, Cin, Hi, Wi], wf from fold_upsample_conv -> [B, Cout, Ho, Wo] (x's dtype)."""
+    import torch.nn.functional as F
+    B, _, Hi, Wi = x.shape
+    ycls, xcls = upsample_axis_classes(Hi, Ho), upsample_axis_classes(Wi, Wo)
+    assert wf.shape[0] == len(ycls) * len(xcls)
+    y = x.new_zeros(B, wf.shape[1], Ho, Wo)
+    for yc, (hn, h0, hp, hpar) in enumerate(ycls):
+        for xc, (wn, w0, wp, wpar) in enumerate(xcls):
+            if hn == 0 or wn == 0:
+                continue
+            w = wf[yc * len(xcls) + xc].to(x.dtype).permute(0, 3, 1, 2)                      # [Cout, Cin, 2, 2]
+            xp = F.pad(x, (1, 1, 1, 1))                                                     # source s sits at s + 1
+            win = xp[:, :, h0 - hp + 1:h0 - hp + 1 + hn + 1, w0 - wp + 1:w0 - wp + 1 + wn + 1]
+            y[:, :, 2 * h0 + hpar:2 * (h0 + hn - 1) + hpar + 1:2, 2 * w0 + wpar:2 * (w0 + wn - 1) + wpar + 1:2] = F.conv2d(win, w)
+    return y if bias is None else y + bias.to(x.dtype)[None, :, None, None]
 
 
 def round_up(x: int, m: int) -> int:

@@ -18,7 +18,7 @@ import torch
 from . import _lib as L
 from . import ops as O
 from . import packing as PK
-from .engine import PackedNet, Pool
+from .engine import PackedNet, Pool, upsample_conv_folds
 
 BF16, F32 = torch.bfloat16, torch.float32
 ZPAD = 8      # latent channels padded 4 -> 8 so conv_in runs on the MFMA path
@@ -129,6 +129,8 @@ class VaeEncodePlan:
 
 
 class VaeDecodePlan:
+    fold_upsample = None                    # the upsamplers as upsampled-2x convs: None = on GPU devices, True / False = forced (engine.upsample_conv_folds)
+
     def __init__(self, vcfg, net: PackedNet, device, n_img: int, latent_hw):
         self.vcfg, self.device, self.n = vcfg, device, n_img
         h, w = latent_hw
@@ -197,6 +199,13 @@ class VaeDecodePlan:
                 x = resnet(x, f"decoder.up_blocks.{i}.resnets.{j}.")
             if i != nlev - 1:
                 H2, W2 = 2 * x.shape[1], 2 * x.shape[2]
+                key = f"decoder.up_blocks.{i}.upsamplers.0.conv."
+                if upsample_conv_folds(device, self.fold_upsample, x.shape[1], x.shape[2], H2, W2, x.shape[3], B=n_img):
+                    wt = net.conv_up2x(key + "weight", False, False)
+                    y = buf(n_img, H2, W2, wt.shape[1])
+                    emit(O.Conv(x, wt, y, bias=net.vec(key + "bias"), ws=self.ws, upsample2x=True, name="vae." + key))
+                    x = y
+                    continue
                 up = buf(n_img, H2, W2, x.shape[3])
                 emit(O.Upsample(x, up, PK.nearest_index(x.shape[1], H2).to(device), PK.nearest_index(x.shape[2], W2).to(device), name=f"vae.up{i}.nearest"))
                 x = conv3(up, f"decoder.up_blocks.{i}.upsamplers.0.conv.")
