@@ -91,7 +91,9 @@ typedef struct MdxGemmDesc {
      * raw columns n >= vt_from are NOT written to C but to Vt[b][n - vt_from][t] with b = m / vt_T, t = m % vt_T
      * (element strides vt_stride per view, vt_ld per channel).  C then has vt_from columns.  Needs K == 320, vt_from % 128 == 0,
      * vt_T % 8 == 0, M % 8 == 0, 16-byte aligned Vt rows, no bias / epilogue on those columns (diffusers' to_v has none) —
-     * it is implemented by the weight-stationary kernel only; anything else is rejected with MDX_EINVAL.  Vt = NULL: off. */
+     * it is implemented by the weight-stationary kernel only; anything else is rejected with MDX_EINVAL.  That kernel reads A through one
+     * 2 GiB window: with Vt the whole extent of A, M * lda * 2 bytes, must stay below 0x7FFF0000 (3.35 M rows of 320), else MDX_EINVAL.
+     * (Without Vt there is no such limit: a K = 320 GEMM whose A is longer runs on a main loop that rebases per tile.)  Vt = NULL: off. */
     void* Vt;
     int64_t vt_from, vt_T, vt_ld, vt_stride;
     /* Optional LayerNorm of the A rows, fused into the projection that consumes them (BasicTransformerBlock: norm1 -> attn1.to_q/k/v,

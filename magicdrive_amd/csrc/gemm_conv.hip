@@ -29,6 +29,7 @@ namespace mdx {
 
 int launch_gemm_ws(const GCParams& p, hipStream_t st);                          // gemm_ws.hip: weight-stationary K = 320 GEMM
 bool ws_supported(const GCParams& p);
+bool ws_fits_window(const GCParams& p);                                            // A within the kernel's one 2 GiB descriptor window
 bool ws_fuses_layernorm(const GCParams& p);
 int launch_layernorm_plain(const bf16_t* X, bf16_t* Y, int M, int C, long ldx, long ldy, float eps, hipStream_t st);   // norm.hip
 int launch_rowstat(const bf16_t* X, int M, int C, long ldx, float* stat, int parts, hipStream_t st);                      // norm.hip
@@ -450,7 +451,7 @@ int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
                           xl_supported(p, false, 256) && (long)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 1024;
     // THE weight-stationary decision: the rowstat_out branch, the fused-LayerNorm branch and the launch below all read ws_taken (a K = 320 GEMM
     // is never claimed by the forced-XL block further down unless XL_K320 is set, and then ws_taken is false).
-    const bool ws_first = !conv && ws_mode > 0 && p.splitk <= 1 && ws_supported(p) && (ws_mode >= 2 || p.M >= 8192);
+    const bool ws_first = !conv && ws_mode > 0 && p.splitk <= 1 && ws_supported(p) && ws_fits_window(p) && (ws_mode >= 2 || p.M >= 8192);
     const bool ws_taken = impl == 0 && !geglu_xl && ws_first && !(xl_k320 && xl_mode > 0);
     if (p.rowstat) {
         // Row statistics of C for the LayerNorm that reads it next (MdxGemmDesc.rowstat_out): the K = 320 weight-stationary kernel emits them

@@ -585,8 +585,13 @@ bool ws_emits_rowstat(const GCParams& p) {
     return p.rowstat && p.epi == 0 && !p.Vt && p.wide && !p.c_f32 && p.ln_eps <= 0.f && (p.N + 127) / 128 <= p.rowstat_parts;
 }
 
+// The activation stream reads A through ONE buffer descriptor based at p.A (tile offsets are 32-bit byte offsets into its 2 GiB window, not
+// rebased per tile): the whole extent of A must fit.  launch_gemm_conv asks this before it takes the route — a longer A goes to a main loop
+// that rebases per tile; only the transposed-V form (no other route) is refused below.
+bool ws_fits_window(const GCParams& p) { return (long)p.M * p.lda * 2 < 0x7FFF0000L; }
+
 int launch_gemm_ws(const GCParams& p, hipStream_t st) {
-    if ((long)p.M * p.lda * 2 >= 0x7FFF0000L) return set_error(MDX_EINVAL, "gemm_ws: A exceeds the 2 GiB buffer window");
+    if (!ws_fits_window(p)) return set_error(MDX_EINVAL, "gemm_ws: A exceeds the 2 GiB buffer window (M * lda * 2 = %ld bytes; the transposed-V output has no other main loop)", (long)p.M * p.lda * 2);
     const bool ln = p.ln_eps > 0.f;
     if (ln && !ws_fuses_layernorm(p)) return set_error(MDX_EINVAL, "gemm_ws: fused LayerNorm needs ln_csum and a plain epilogue (GEGLU: also ln_stats)");
     const bool lns = ln && p.ln_stats != nullptr;

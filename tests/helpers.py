@@ -103,3 +103,88 @@ def check(name, value, limit):
         assert value == value and value < 10 * limit, (name, value, limit)      # report mode still refuses garbage
         return
     assert value < limit, f"{name}: {value:.4e} >= {limit:.1e}"
+
+
+def _periodic_index(index, lo, hi, device):
+    """Base rows of the output rows lo..hi-1: `index` is the period P (row m <-> base[m % P]) or a function (lo, hi, device) -> int64 tensor."""
+    if callable(index):
+        return index(lo, hi, device).to(device=device, dtype=torch.int64)
+    return torch.arange(lo, hi, device=device, dtype=torch.int64) % int(index)
+
+
+def close_periodic(out, ref_base, index, name="", kind=None, max_rel_l2=None, chunk_bytes=256 << 20):
+    """close() for an output too large for a full-size reference: `out` repeats along dim 0 (rows of a GEMM, images of a conv, batch items of an
+    attention), out[m] <-> ref_base[index(m)] with `index` a period P (m % P) or a function (lo, hi, device) -> base indices.  The output is
+    walked in dim-0 slices of at most ~chunk_bytes of fp32 on its own device; the same three quantities as close() are accumulated over the
+    WHOLE tensor (fraction over tol, worst err / tol, rel L2; tol = atol_rel * mean|ref| + rtol * |ref| with the mean taken over the whole
+    expanded reference) and held to the same limits from the same XF_ATOL / XF_RTOL tables; every element must be finite.  One parity_log
+    line; REPORT_ONLY as in close()."""
+    kind = kind or DEFAULT_KIND
+    if max_rel_l2 is None:
+        max_rel_l2 = 4e-3 if kind == "bf16" else 6e-4
+    rtol, atol_rel = XF_RTOL[kind], XF_ATOL[kind]
+    dev = out.device
+    ref_base = ref_base.to(device=dev, dtype=torch.float32)
+    n0 = out.shape[0]
+    assert tuple(out.shape[1:]) == tuple(ref_base.shape[1:]) and n0 > 0, (name, tuple(out.shape), tuple(ref_base.shape))
+    per = max(1, out[0].numel())
+    step = max(1, int(chunk_bytes // (4 * per)))
+    # mean |ref| of the expanded reference: how often each base row occurs, times its own sum
+    counts = torch.zeros(ref_base.shape[0], dtype=torch.float64, device=dev)
+    for lo in range(0, n0, max(step, 1 << 20)):
+        hi = min(n0, lo + max(step, 1 << 20))
+        idx = _periodic_index(index, lo, hi, dev)
+        assert idx.numel() == hi - lo and int(idx.min()) >= 0 and int(idx.max()) < ref_base.shape[0], (name, "index out of the base")
+        counts += torch.bincount(idx, minlength=ref_base.shape[0]).double()
+    row_abs = ref_base.abs().double().reshape(ref_base.shape[0], -1).sum(1)
+    scale = float((counts * row_abs).sum() / (float(n0) * per)) + 1e-6
+    n_bad = torch.zeros((), dtype=torch.float64, device=dev)
+    se = torch.zeros((), dtype=torch.float64, device=dev); sr = torch.zeros((), dtype=torch.float64, device=dev)
+    worst = torch.zeros((), dtype=torch.float32, device=dev); max_err = torch.zeros((), dtype=torch.float32, device=dev)
+    n_nonfinite = torch.zeros((), dtype=torch.float64, device=dev)
+    first_bad = None
+    for lo in range(0, n0, step):
+        hi = min(n0, lo + step)
+        o = out[lo:hi].float()
+        r = ref_base.index_select(0, _periodic_index(index, lo, hi, dev))
+        fin = torch.isfinite(o)
+        n_nonfinite += (~fin).sum().double()
+        err = torch.where(fin, (o - r).abs(), torch.full_like(o, float("inf")))
+        ratio = err / (atol_rel * scale + rtol * r.abs())
+        n_bad += (ratio > 1.0).sum().double()
+        worst = torch.maximum(worst, ratio.max()); max_err = torch.maximum(max_err, err.max())
+        se += err.double().pow(2).sum(); sr += r.double().pow(2).sum()
+        if first_bad is None:
+            rows_bad = (ratio.reshape(hi - lo, -1).amax(1) > 1.5).nonzero()
+            if rows_bad.numel():
+                first_bad = lo + int(rows_bad[0])
+        del o, r, fin, err, ratio
+    bad = float(n_bad) / (float(n0) * per)
+    worst = float(worst); rel = float(se.sqrt() / (sr.sqrt() + 1e-12)); max_err = float(max_err); nonfinite = int(n_nonfinite)
+    parity_log("close_periodic:" + name, kind=kind, rel_l2=rel, worst_err_over_tol=worst, frac_over_tol=bad, max_err=max_err, scale=scale,
+               rows=n0, elems=n0 * per, nonfinite=nonfinite, first_bad_row=first_bad)
+    assert nonfinite == 0, f"{name}: {nonfinite} non-finite elements, first bad dim-0 index {first_bad}"
+    if REPORT_ONLY:
+        return
+    assert bad <= 1e-4 and worst <= 1.5 and rel < max_rel_l2, (f"{name}: frac_over_tol={bad:.2e} worst err/tol={worst:.2f} rel_l2={rel:.3e} max_err={max_err:.3e} "
+                                                                 f"scale={scale:.3e} first dim-0 index over 1.5 tol={first_bad}")
+
+
+def periodic_mismatch(out, period, chunk_bytes=256 << 20):
+    """Number of dim-0 slices m >= period of `out` that are not bit-identical to slice m - period (walked in chunks), and the first such m."""
+    n0 = out.shape[0]
+    per = max(1, out[0].numel() * out.element_size())
+    step = max(1, int(chunk_bytes // per))
+    total, first = 0, None
+    for lo in range(period, n0, step):
+        hi = min(n0, lo + step)
+        a, b = out[lo:hi], out[lo - period:hi - period]
+        if a.is_floating_point():          # compare bit patterns (NaN == NaN, -0 != +0)
+            it = {2: torch.int16, 4: torch.int32, 8: torch.int64}[a.element_size()]
+            a, b = a.contiguous().view(it), b.contiguous().view(it)
+        diff = (a != b).reshape(hi - lo, -1).any(1)
+        n = int(diff.sum())
+        if n and first is None:
+            first = lo + int(diff.nonzero()[0])
+        total += n
+    return total, first

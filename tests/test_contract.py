@@ -317,6 +317,11 @@ TABLE += [
     (L.OP_UNIPC, f"xin_c, xin_ld, gv_last_step {_INT}", unipc(xin_ld=BIG, xin_c=4, x_in=P(8)), EINVAL, "xin_ld="),
     (L.OP_UNIPC, f"xin_c, xin_ld, gv_last_step {_INT}", unipc(gv_last_step=BIG), EINVAL, "gv_last_step="),
 ]
+# rows added later go HERE, at the end: the test ids carry the row's index in TABLE
+TABLE += [
+    (L.OP_GEMM, "Vt: A (M * lda * 2 bytes) below 0x7FFF0000", gemm(M=3355520, N=256, K=320, lda=320, ldw=320, ldc=128, Vt=P(5), vt_from=128, vt_T=8, vt_ld=8, vt_stride=1024),
+     EINVAL, "2 GiB buffer window"),
+]
 
 
 def _desc(opcode, fields):

@@ -564,3 +564,36 @@ def test_unipc_host_step_api_reproduces_the_diffusers_kat(monkeypatch):
         for t in s2.set_timesteps(6):
             z = s2.step(z * f, t, z).prev_sample
         assert torch.equal(z, y)
+
+
+def test_close_periodic_finds_one_corrupted_row_past_the_first_period(tmp_path, monkeypatch):
+    """helpers.close_periodic (tests/test_large_gpu.py) on a tiny synthetic tensor: passes on the periodic expansion of a 16-bit-rounded
+    base walked in many chunks, with the numbers helpers.close gives for the fully expanded reference; ONE corrupted row beyond the first
+    period fails it and is named; a NaN fails it; an index function works like the period."""
+    import json
+    import helpers
+    monkeypatch.setenv("MDX_PARITY_LOG", str(tmp_path / "parity.jsonl"))
+    monkeypatch.setattr(helpers, "REPORT_ONLY", False)
+    P, M = 7, 45
+    base = torch.randn(P, 6, generator=torch.Generator().manual_seed(0))
+    idx = torch.arange(M) % P
+    out = (base[idx] * (1 + 1e-3)).to(torch.bfloat16)
+    helpers.close_periodic(out, base, P, name="ok", kind="bf16", chunk_bytes=100)                # 4 rows per chunk
+    helpers.close(out, base[idx], name="ok-full", kind="bf16")
+    helpers.close_periodic(out, base, lambda lo, hi, dev: torch.arange(lo, hi, device=dev) % P, name="ok-fn", kind="bf16", chunk_bytes=100)
+    rows = [json.loads(l) for l in open(tmp_path / "parity.jsonl")]
+    for key in ("rel_l2", "worst_err_over_tol", "frac_over_tol", "max_err", "scale"):
+        assert abs(rows[0][key] - rows[1][key]) <= 2e-6 * max(1.0, abs(rows[1][key])), (key, rows[0][key], rows[1][key])
+        assert rows[2][key] == rows[0][key]
+    assert helpers.periodic_mismatch(out, P, chunk_bytes=100) == (0, None)
+    bad = out.clone(); bad[3 * P + 2, 4] += 0.25                                                 # row 23: fourth period
+    with pytest.raises(AssertionError, match="index over 1.5 tol=23"):
+        helpers.close_periodic(bad, base, P, name="corrupt", kind="bf16", chunk_bytes=100)
+    assert helpers.periodic_mismatch(bad, P, chunk_bytes=100) == (2, 23)                          # rows 23 and 30 differ from their predecessors
+    nan = out.clone(); nan[M - 1, 0] = float("nan")
+    with pytest.raises(AssertionError, match="non-finite"):
+        helpers.close_periodic(nan, base, P, name="nan", kind="bf16", chunk_bytes=100)
+    monkeypatch.setattr(helpers, "REPORT_ONLY", True)                                            # report mode records; garbage (NaN) still fails
+    helpers.close_periodic(bad, base, P, name="report", kind="bf16", chunk_bytes=100)
+    with pytest.raises(AssertionError):
+        helpers.close_periodic(nan, base, P, name="report-nan", kind="bf16", chunk_bytes=100)
