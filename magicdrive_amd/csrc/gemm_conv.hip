@@ -27,15 +27,12 @@
 namespace mdx {
 
 
+using namespace mdx_route;
+
 int launch_gemm_ws(const GCParams& p, hipStream_t st);                          // gemm_ws.hip: weight-stationary K = 320 GEMM
-bool ws_supported(const GCParams& p);
-bool ws_fits_window(const GCParams& p);                                            // A within the kernel's one 2 GiB descriptor window
-bool ws_fuses_layernorm(const GCParams& p);
+int launch_gemm_xl(const GCParams& p, bool conv, int bn, hipStream_t st);       // gemm_xl.hip: 256 x {320,256,160} LDS-DMA quadrant-phase tiles
 int launch_layernorm_plain(const bf16_t* X, bf16_t* Y, int M, int C, long ldx, long ldy, float eps, hipStream_t st);   // norm.hip
 int launch_rowstat(const bf16_t* X, int M, int C, long ldx, float* stat, int parts, hipStream_t st);                      // norm.hip
-bool ws_emits_rowstat(const GCParams& p);                                                                                  // gemm_ws.hip
-int launch_gemm_xl(const GCParams& p, bool conv, int bn, hipStream_t st);       // gemm_xl.hip: 256 x {256,160} LDS-DMA quadrant-phase tiles
-bool xl_supported(const GCParams& p, bool conv, int bn);
 
 // WM x WN waves (NTH = 64 WM WN threads); each wave owns a (BM/WM) x (BN/WN) sub-tile of 32x32 MFMA tiles.
 template <int BM, int BN, int BK, int WM, int WN, bool CONV, bool PIPE>
@@ -382,8 +379,9 @@ static int launch_one_(const GCParams& p, hipStream_t st) {
     const unsigned nblk = q.swz ? (unsigned)((q.mt + 7) / 8 * 8 * q.nt) : (unsigned)(q.mt * q.nt);
     dim3 grid(nblk, 1, p.batch > 1 ? p.batch : p.splitk);
     hipLaunchKernelGGL(kern, grid, dim3(WM * WN * 64), smem, st, q);
+    static_assert(WM == (BM == 256 ? 4 : 2) && WN == 2, "tag_generic derives the wave grid from BM");
     char tag[96];
-    snprintf(tag, sizeof tag, "gemm_conv_kernel<%d,%d,%d,%d,%d,%s>", BM, BN, BK, WM, WN, CONV ? "conv" : "gemm");
+    tag_generic(tag, sizeof tag, BM, BN, BK, CONV);
     return check_launch(tag);
 }
 
@@ -397,196 +395,92 @@ static int launch_one(const GCParams& p, hipStream_t st) {
     return launch_one_<BM, BN, BK, WM, WN, CONV, false>(p, st);
 }
 
-// Routing (four main loops; options.h lists the switches, all settable in-process through mdx_set_option):
-//   gemm_ws.hip   K = 320 projections / GEGLU with M >= 8192 (level 0 of the UNet): weights in registers, activations streamed
-//   gemm_xl.hip   every conv with Cin % 64 == 0 and every GEMM with K % 64 == 0 that yields >= xl_min_tiles 256-row tiles
-//                 (>= ~8 scenes per GPU at level 0, >= ~32 at the 7x13 level): 256 x {160, 256, 320} LDS-DMA tiles
-//   this file     everything else: 128 / 64-row register-staged tiles (64 x 64 for small grids), split-K for the 7x13 / 4x7 levels at small batches
+static_assert(R_EINVAL == MDX_EINVAL && R_EUNSUPPORTED == MDX_EUNSUPPORTED, "gemm_route.h error codes");
+
+RouteIn route_in(const GCParams& p, bool conv) {
+    RouteIn r = {};
+    r.M = p.M; r.N = p.N; r.K = p.K; r.batch = p.batch; r.splitk = p.splitk; r.epi = p.epi;
+    r.c_f32 = p.c_f32 != 0; r.conv = conv;
+    r.Hi = p.Hi; r.Wi = p.Wi; r.Cin = p.Cin; r.Ho = p.Ho; r.Wo = p.Wo; r.kh = p.kh; r.kw = p.kw; r.sh = p.sh; r.sw = p.sw; r.ph = p.ph; r.pw = p.pw;
+    r.cimajor = p.cimajor != 0; r.up2 = p.up2 != 0; r.upB = p.upB;
+    r.lda = p.lda; r.ldw = p.ldw; r.ldc = p.ldc; r.ldr = p.ldr; r.sC = p.sC;
+    r.rows_per_b = p.rows_per_b; r.col_split = p.col_split;
+    r.ws_bytes = p.ws_bytes; r.has_ws = p.ws != nullptr;
+    r.bias = p.bias != nullptr; r.temb = p.temb != nullptr; r.R = p.R != nullptr; r.Vt = p.Vt != nullptr; r.Wq = p.Wq != nullptr;
+    r.ln_csum = p.ln_csum != nullptr; r.ln_scratch = p.ln_scratch != nullptr;
+    r.ln_stats = p.ln_stats != nullptr; r.ln_stats_parts = p.ln_stats_parts;
+    r.rowstat = p.rowstat != nullptr; r.rowstat_parts = p.rowstat_parts;
+    r.ln = p.ln_eps > 0.f; r.wide = p.wide != 0;
+    r.r_al16 = (((uintptr_t)p.R) & 15) == 0; r.wq_al16 = (((uintptr_t)p.Wq) & 15) == 0; r.bias_al16 = (((uintptr_t)p.bias) & 15) == 0;
+    return r;
+}
+
+static RouteOpts route_opts() {
+    RouteOpts o;
+#define MDX_RO(key) o.key = (int)opt(OPT_##key);
+    MDX_RO(GEMM_WS) MDX_RO(GEMM_XL) MDX_RO(XL_K320) MDX_RO(XL_MIN_TILES) MDX_RO(XL_BN) MDX_RO(XL_GEGLU320) MDX_RO(GEMM_SMALL_TILES) MDX_RO(GEMM_BM256)
+    MDX_RO(GEMM_BM) MDX_RO(GEMM_BN) MDX_RO(GEMM_BK) MDX_RO(GEMM_FLATTEN) MDX_RO(LN_FUSE) MDX_RO(LN_STATS) MDX_RO(GEMM_TIMING)
+#undef MDX_RO
+    return o;
+}
+
+// LayerNorm of the A rows (no affine part: it is in W / bias) into the caller's scratch; the GEMM then reads the normalised copy
+static int normalise_first(GCParams& p, hipStream_t st) {
+    if (int rc = launch_layernorm_plain(p.A, p.ln_scratch, p.M, p.K, p.lda, p.lda, p.ln_eps, st)) return rc;
+    p.A = p.ln_scratch; p.ln_eps = 0.f; p.ln_csum = nullptr; p.ln_stats = nullptr; p.ln_stats_parts = 0;
+    return MDX_OK;
+}
+
+// The register-staged tile of this file, split-K slabs reduced behind it
+static int launch_generic(const GCParams& p, bool conv, int BM, int BN, int BK, hipStream_t st) {
+    int rc;
+#define MDX_GC2(BM_, BN_, BK_, WM_, WN_) (conv ? launch_one<BM_, BN_, BK_, WM_, WN_, true>(p, st) : launch_one<BM_, BN_, BK_, WM_, WN_, false>(p, st))
+#define MDX_GC(BM_, BN_) (BK == 32 ? MDX_GC2(BM_, BN_, 32, 2, 2) : MDX_GC2(BM_, BN_, 64, 2, 2))
+    if (BM == 256 && BN == 128) rc = (BK == 32) ? MDX_GC2(256, 128, 32, 4, 2) : MDX_GC2(256, 128, 64, 4, 2);
+    else if (BM == 128 && BN == 128) rc = MDX_GC(128, 128);
+    else if (BM == 128 && BN == 64) rc = MDX_GC(128, 64);
+    else if (BM == 64 && BN == 128) rc = MDX_GC(64, 128);
+    else rc = MDX_GC(64, 64);
+#undef MDX_GC2
+#undef MDX_GC
+    if (rc != MDX_OK || p.splitk <= 1) return rc;
+    const long n = (long)p.M * (p.N / 4);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
+    return check_launch("splitk_reduce_kernel", false);
+}
+
+// Executes the route gemm_route (gemm_route.h) picks: pre-step, main launch (+ split-K reduce), post-step.
 // (round 3 removed gemm_dma.hip — an LDS-DMA ring that never beat register staging — and gemm_pp.hip, whose 256 x 256 ping-pong tile
 // was superseded by gemm_xl.hip at every batch where it used to be chosen; round 6 removed conv3x3.hip — one A slab shared by the three
 // horizontal taps on a 128 x 128 tile — which by then only 1- and 2-scene calls reached and which ran 8-12 % behind the generic tile
 // there: 56 vs 50 us for the level-0 320 -> 320 conv at one scene, profiles/r06_lat1_small_grids.log.)
 int launch_gemm_conv(GCParams p, bool conv, hipStream_t st) {
     if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MDX_OK;
-    const bool geglu = p.epi == 1;
     {   // 16-byte epilogue accesses need 16-byte aligned rows of C and R and whole 8-column chunks
-        const long nout = geglu ? p.N / 2 : p.N;
+        const long nout = p.epi == 1 ? p.N / 2 : p.N;
         const int wide_on = (int)opt(OPT_EPI_WIDE);
         p.wide = wide_on && !p.c_f32 && (nout % 8) == 0 && (p.ldc % 8) == 0 && (p.sC % 8) == 0 && (((uintptr_t)p.C) & 15) == 0 &&
                  (!p.R || ((p.ldr % 8) == 0 && (p.sR % 8) == 0 && (((uintptr_t)p.R) & 15) == 0));
     }
-    if (p.up2) {
-        // upsampled-2x conv (MdxConvDesc.upsample2x): only the XL main loop knows the mode; the width by the same time model as try_xl below
-        if (!conv) return set_error(MDX_EINVAL, "upsample2x: conv only");
-        int bn_up = 0; double best = 1e300;
-        const int mt = up_mtiles(p);
-        for (int bn : {320, 256}) {
-            if (!xl_supported(p, true, bn)) continue;
-            const long t = (long)mt * ((p.N + bn - 1) / bn);
-            const double a = bn == 320 ? 23.7 : 13.4, b = bn == 320 ? 1.896 : 1.565;
-            const double c = (double)((t + 255) / 256) * (a + b * p.K / 64.0);
-            if (c < best) { best = c; bn_up = bn; }
-        }
-        if (const int xl_bn = (int)opt(OPT_XL_BN)) if ((xl_bn == 320 || xl_bn == 256) && xl_supported(p, true, xl_bn)) bn_up = xl_bn;
-        if (!bn_up) return set_error(MDX_EINVAL, "mdx_conv2d: upsample2x needs Cin %% 64 == 0, Ho in {2 Hi, 2 Hi - 1}, Wo in {2 Wi, 2 Wi - 1}, bias-only epilogue, no split-K; with a cropped axis B * Hi * Wi * ldx * 2 < 2^31");
-        return launch_gemm_xl(p, true, bn_up, st);
-    }
-    if (!opt(OPT_LN_STATS)) { p.rowstat = nullptr; p.rowstat_parts = 0; p.ln_stats = nullptr; p.ln_stats_parts = 0; }   // A/B: the round-5 data flow
-    if (geglu && (p.N % 64) != 0) return set_error(MDX_EINVAL, "GEGLU needs packed N %% 64 == 0 (N=%d)", p.N);
-    constexpr int impl = 0;
-    // K = 320 projections with many rows: weights in registers, activations streamed (gemm_ws.hip).  MDX_GEMM_WS: 0 off, 1 when
-    // M >= 8192 (default), 2 whenever supported.
-    const int ws_mode = (int)opt(OPT_GEMM_WS);
-    // Large shapes: the LDS-DMA quadrant-phase kernel (gemm_xl.hip).  MDX_GEMM_XL: 0 off, 1 cost model (default), 2 whenever supported.
-    // Tile width: 256 columns, or 160 when that wastes fewer padded columns (N = 320 / 640 / 960 / 1920); a launch must give most of
-    // the 256 CUs a tile (one workgroup per CU).  MDX_XL_K320 = 1 lets it take the K = 320 projections from gemm_ws.hip as well.
-    const int xl_mode = (int)opt(OPT_GEMM_XL);
-    const int xl_k320 = (int)opt(OPT_XL_K320);
-    const int xl_min_tiles = (int)opt(OPT_XL_MIN_TILES);
-    // K = 320 GEGLU with many rows: gemm_ws.hip (384 views: 1642 us) vs the 256 x 256 XL tile (1694-1757 us).  Before the ring of
-    // gemm_ws.hip really ran ahead (its DMA builtin drained the VM counter every slab: 1994 us) the XL tile was the faster one;
-    // MDX_XL_GEGLU320=1 selects it again.
-    const int xl_geglu320 = (int)opt(OPT_XL_GEGLU320);
-    const bool geglu_xl = xl_geglu320 && xl_mode == 1 && impl == 0 && !conv && geglu && p.K == 320 && p.splitk <= 1 && ws_mode < 2 &&
-                          xl_supported(p, false, 256) && (long)((p.M + 255) / 256) * ((p.N + 255) / 256) >= 1024;
-    // THE weight-stationary decision: the rowstat_out branch, the fused-LayerNorm branch and the launch below all read ws_taken (a K = 320 GEMM
-    // is never claimed by the forced-XL block further down unless XL_K320 is set, and then ws_taken is false).
-    const bool ws_first = !conv && ws_mode > 0 && p.splitk <= 1 && ws_supported(p) && ws_fits_window(p) && (ws_mode >= 2 || p.M >= 8192);
-    const bool ws_taken = impl == 0 && !geglu_xl && ws_first && !(xl_k320 && xl_mode > 0);
-    if (p.rowstat) {
-        // Row statistics of C for the LayerNorm that reads it next (MdxGemmDesc.rowstat_out): the K = 320 weight-stationary kernel emits them
-        // from its store phase; every other route gets them from a small kernel over the finished C (part 0 = whole rows, the rest zeros).
-        // Past this block only launch_gemm_ws may see p.rowstat: the other launchers refuse it.
-        if (conv || p.batch > 1 || p.epi != 0 || p.c_f32 || p.Vt || p.rowstat_parts < 1) return set_error(MDX_EINVAL, "rowstat_out: plain 2-D GEMM with 16-bit C only");
-        if (!(ws_taken && ws_emits_rowstat(p) && opt(OPT_LN_FUSE))) {
-            GCParams q = p;
-            q.rowstat = nullptr; q.rowstat_parts = 0;
-            if (int rc = launch_gemm_conv(q, conv, st)) return rc;
-            return launch_rowstat((const bf16_t*)p.C, p.M, p.N, p.ldc, p.rowstat, p.rowstat_parts, st);
-        }
-    }
-    // Width choice: time model fitted on MI355X at 384 views (profiles/README.md, round 2): a tile costs a(bn) + b(bn) * K/64
-    // microseconds — b falls with the tile width (operand bytes per MAC through the global -> LDS path), a (prologue + the
-    // HBM-bound epilogue burst; the 320-wide tile stages C in two halves) rises — times the rounds of tiles over the 256 CUs.
-    auto try_xl = [&](int& bn_out) -> bool {
-        if (impl != 0 || xl_mode <= 0 || p.splitk > 1) return false;
-        const int xl_bn = (int)opt(OPT_XL_BN);   // benchmarking: force a width
-        double best = 1e300;
-        bn_out = 0;
-        const double nslab = p.K / 64.0;
-        for (int bn : {320, 256, 160}) {
-            if (xl_bn && bn != xl_bn) continue;
-            if (!xl_supported(p, conv, bn)) continue;
-            const long t = (long)((p.M + 255) / 256) * ((p.N + bn - 1) / bn);
-            if (xl_mode < 2 && t < xl_min_tiles) continue;
-            const double a = bn == 320 ? 23.7 : bn == 256 ? 13.4 : 16.6, b = bn == 320 ? 1.896 : bn == 256 ? 1.565 : 1.116;
-            const double c = (double)((t + 255) / 256) * (a + b * nslab);
-            if (c < best) { best = c; bn_out = bn; }
-        }
-        return bn_out != 0;
-    };
-    if (p.ln_eps > 0.f) {
-        // LayerNorm fused into this GEMM (MdxGemmDesc.ln_eps): the weight-stationary kernel normalises in-kernel; every other route gets
-        // the rows normalised (no affine part: it is in W / bias) into the caller's scratch first.
-        if (conv || p.batch > 1) return set_error(MDX_EINVAL, "fused LayerNorm: plain 2-D GEMM only");
-        if (!(ws_taken && ws_fuses_layernorm(p) && opt(OPT_LN_FUSE))) {
-            if (!p.ln_scratch) return set_error(MDX_EINVAL, "fused LayerNorm: this shape is not normalised in-kernel and no ln_scratch was given");
-            if (int rc = launch_layernorm_plain(p.A, p.ln_scratch, p.M, p.K, p.lda, p.lda, p.ln_eps, st)) return rc;
-            p.A = p.ln_scratch; p.ln_eps = 0.f; p.ln_csum = nullptr; p.ln_stats = nullptr; p.ln_stats_parts = 0;
-        }
-    }
-    if (xl_mode >= 2 && p.splitk <= 1 && p.batch <= 1 && !(p.K == 320 && !conv && !xl_k320)) {
-        // "whenever supported" (tests / benchmarking): ahead of the automatic split-K below, which would otherwise claim small grids
-        GCParams q = p;
-        q.splitk = 1;
-        int bn_f;
-        const int keep = p.splitk;
-        p.splitk = 1;
-        const bool ok = try_xl(bn_f);
-        p.splitk = keep;
-        if (ok) return launch_gemm_xl(q, conv, bn_f, st);
-    }
-    if (geglu_xl) return launch_gemm_xl(p, false, 256, st);
-    if (ws_taken) return launch_gemm_ws(p, st);
-    int BM, BN;
-    {
-        BN = 128;
-        if (!geglu && (p.N <= 64 || (p.N % 128 != 0 && p.N <= 192))) BN = 64;
-        BM = p.M >= 2048 ? 128 : 64;
-        // Small grids (round 6; the reference's own operating point is 1-4 scenes per call, where every launch of the step program lands here): with fewer
-        // workgroups than the chip has room for, the SMALLER tile is the faster one — four 64 x 64 workgroups share a CU (37 KB of LDS each) where two
-        // 128 x 128 ones fit, and a 4-wave workgroup alone on its CU has nothing to run beside its load phase.  Measured over every GEMM / conv shape
-        // of the 1-, 2- and 4-scene step programs under forced tiles (tools/tile_sweep.py, profiles/r06_tile_sweep.log): plain GEMMs are fastest on
-        // 64 x 64 up to ~1400 such tiles (9.5 vs 14.7 us at M 2100, N = K = 640; 18.7 vs 28.4 us at M 2184, N = K = 1280); implicit-GEMM convs up to
-        // ~40 k (tile, slab) units of work, beyond that on 128 x 128 — never on the 64 x 128 tile rounds 1-5 gave every M < 2048; GEGLU (needs 128
-        // columns) on 128 rows from M = 512.  Same k order in every tile: results do not depend on the choice (split-K aside).
-        if (opt(OPT_GEMM_SMALL_TILES) && p.batch <= 1) {
-            const long t64 = (long)((p.M + 63) / 64) * ((p.N + 63) / 64);
-            if (geglu) {
-                BM = p.M >= 512 ? 128 : 64;
-            } else if (!conv) {
-                if (t64 <= 1408) BM = BN = 64;
-            } else if (t64 * (long)((p.K + 63) / 64) <= 40000) {
-                BM = BN = 64;
-            } else if (BN == 128) {
-                BM = 128;
-            }
-        }
-        const int big = (int)opt(OPT_GEMM_BM256);
-        if (big && BN == 128 && p.M >= big) BM = 256;
-        const int fbm = (int)opt(OPT_GEMM_BM), fbn = (int)opt(OPT_GEMM_BN);
-        if (fbm == 64 || fbm == 128) BM = fbm;
-        if ((fbn == 64 && !geglu) || fbn == 128) BN = fbn;
-    }
-    long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * (p.batch > 1 ? p.batch : 1);
-    int splitk = 1;
-    if (p.splitk > 0) {
-        splitk = p.splitk;  // caller forced
-    } else if (p.batch <= 1 && p.ws && tiles < 384 && p.K >= 1024 && (p.N % 4) == 0) {
-        long want = (768 + tiles - 1) / tiles;
-        long maxs = p.K / 512;  // keep >= 8 K-slabs per slice
-        splitk = (int)min(min(want, maxs), 32L);
-        if (splitk < 1) splitk = 1;
-    }
-    if (p.batch > 1) splitk = 1;
-    if (splitk > 1) {  // fit the fp32 slabs into the caller's workspace
-        long per = (long)p.M * p.N * (long)sizeof(float);
-        long fit = per > 0 ? p.ws_bytes / per : 0;
-        if (fit < splitk) splitk = fit < 1 ? 1 : (int)fit;
-    }
-    constexpr int BK = 64;   // split-K slices are multiples of the largest slab
-    int kchunk = ((p.K + splitk - 1) / splitk + BK - 1) / BK * BK;
-    splitk = (p.K + kchunk - 1) / kchunk;
-    if (splitk > 1 && !p.ws) return set_error(MDX_EINVAL, "split-K needs a workspace");
-    p.splitk = splitk;
-    p.kchunk = kchunk;
-    const int timing = (int)opt(OPT_GEMM_TIMING);
-    p.timing = (timing && p.ws && splitk == 1) ? (unsigned long long*)p.ws : nullptr;
-    if (splitk == 1) {
-        int bn_xl;
-        if (try_xl(bn_xl)) return launch_gemm_xl(p, conv, bn_xl, st);
-    }
-    if (impl == 0 && ws_first) return launch_gemm_ws(p, st);       // MDX_XL_K320 was set but the XL kernel declined the shape
+    const Route r = gemm_route(route_in(p, conv), route_opts());
+    if (r.err) return set_error(r.err, r.msg, r.arg);
+    if (r.normalise_first) if (int rc = normalise_first(p, st)) return rc;
+    float* const rowstat = p.rowstat; const int rowstat_parts = p.rowstat_parts;
+    // Past this point only launch_gemm_ws may see p.rowstat (and only when the route keeps it): the other launchers refuse it.
+    if (!r.keep_rowstat) { p.rowstat = nullptr; p.rowstat_parts = 0; }
+    if (!r.keep_ln_stats) { p.ln_stats = nullptr; p.ln_stats_parts = 0; }
     int rc;
-    {
-        const int bk = (int)opt(OPT_GEMM_BK);
-#define MDX_GC2(BM_, BN_, BK_, WM_, WN_) (conv ? launch_one<BM_, BN_, BK_, WM_, WN_, true>(p, st) : launch_one<BM_, BN_, BK_, WM_, WN_, false>(p, st))
-#define MDX_GC(BM_, BN_) (bk == 32 ? MDX_GC2(BM_, BN_, 32, 2, 2) : MDX_GC2(BM_, BN_, 64, 2, 2))
-        if (BM == 256 && BN == 128) rc = (bk == 32) ? MDX_GC2(256, 128, 32, 4, 2) : MDX_GC2(256, 128, 64, 4, 2);
-        else if (BM == 128 && BN == 128) rc = MDX_GC(128, 128);
-        else if (BM == 128 && BN == 64) rc = MDX_GC(128, 64);
-        else if (BM == 64 && BN == 128) rc = MDX_GC(64, 128);
-        else rc = MDX_GC(64, 64);
-#undef MDX_GC2
-#undef MDX_GC
+    if (r.main == MAIN_XL) {
+        rc = launch_gemm_xl(p, conv, r.bn, st);
+    } else if (r.main == MAIN_WS) {
+        rc = launch_gemm_ws(p, st);
+    } else {
+        p.splitk = r.splitk; p.kchunk = r.kchunk;
+        p.timing = r.timing ? (unsigned long long*)p.ws : nullptr;
+        rc = launch_generic(p, conv, r.BM, r.BN, r.BK, st);
     }
-    if (rc != MDX_OK) return rc;
-    if (splitk > 1) {
-        long n = (long)p.M * (p.N / 4);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, p);
-        return check_launch("splitk_reduce_kernel", false);
-    }
-    return MDX_OK;
+    if (rc != MDX_OK || !r.rowstat_after) return rc;
+    return launch_rowstat((const bf16_t*)p.C, p.M, p.N, p.ldc, rowstat, rowstat_parts, st);
 }
 
 }  // namespace mdx
@@ -620,24 +514,6 @@ static int check_epilogue_operands(const char* op, const void* R, const float* b
         MDX_NEED(need_multiple(op, "temb_b_stride", temb_b_stride, 4));
     }
     return MDX_OK;
-}
-
-// One XL launch for a batch-flattened GEMM (see mdx_gemm_bf16); MDX_EUNSUPPORTED when the XL kernel does not take the shape.
-static int launch_gemm_flat(const mdx::GCParams& q, hipStream_t st) {
-    using namespace mdx;
-    const int xl_mode = (int)opt(OPT_GEMM_XL);
-    if (xl_mode <= 0) return MDX_EUNSUPPORTED;
-    double best = 1e300; int bn_best = 0;
-    for (int bn : {320, 256, 160}) {
-        if (!xl_supported(q, false, bn)) continue;
-        const long t = (long)((q.M + 255) / 256) * ((q.N + bn - 1) / bn);
-        if (t < 128) continue;
-        const double a = bn == 320 ? 23.7 : bn == 256 ? 13.4 : 16.6, b = bn == 320 ? 1.896 : bn == 256 ? 1.565 : 1.116;
-        const double c = (double)((t + 255) / 256) * (a + b * q.K / 64.0);
-        if (c < best) { best = c; bn_best = bn; }
-    }
-    if (!bn_best) return MDX_EUNSUPPORTED;
-    return launch_gemm_xl(q, false, bn_best, st);
 }
 
 extern "C" int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream) {
@@ -694,14 +570,13 @@ extern "C" int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream) {
     }
     if (d->Vt) {   // fused q/k/v projection with a transposed V output: weight-stationary kernel only
         p.Vt = (bf16_t*)d->Vt; p.vt_from = (int)d->vt_from; p.vt_T = (int)d->vt_T; p.vt_ld = d->vt_ld; p.vt_stride = d->vt_stride;
-        if (!ws_supported(p) || d->epilogue || d->R || (d->vt_from % 128) || d->vt_from <= 0 || d->vt_from >= d->N || d->vt_T <= 0 ||
+        if (!ws_supported(route_in(p, false)) || d->epilogue || d->R || (d->vt_from % 128) || d->vt_from <= 0 || d->vt_from >= d->N || d->vt_T <= 0 ||
             (d->vt_T % 8) || (d->M % d->vt_T) || (d->vt_ld % 8) || (d->vt_stride % 8) || ((uintptr_t)d->Vt & 15))
             return set_error(MDX_EINVAL, "mdx_gemm_bf16: transposed V output needs K=320, plain epilogue, no residual, vt_from %% 128 == 0, vt_T %% 8 == 0, aligned Vt");
         if (!opt(OPT_LN_STATS)) { p.ln_stats = nullptr; p.ln_stats_parts = 0; }
         if (p.ln_eps > 0.f && !opt(OPT_LN_FUSE)) {            // A/B switch: normalised copy first, then the plain fused q/k/v launch pair
             if (!p.ln_scratch) return set_error(MDX_EINVAL, "fused LayerNorm: LN_FUSE=0 needs ln_scratch");
-            if (int rc2 = launch_layernorm_plain(p.A, p.ln_scratch, p.M, p.K, p.lda, p.lda, p.ln_eps, (hipStream_t)stream)) return rc2;
-            p.A = p.ln_scratch; p.ln_eps = 0.f; p.ln_csum = nullptr; p.ln_stats = nullptr; p.ln_stats_parts = 0;
+            if (int rc2 = normalise_first(p, (hipStream_t)stream)) return rc2;
         }
         { GCParams q = p; const long nout = d->vt_from;      // wide-path check of the C part
           q.wide = (nout % 8) == 0 && (p.ldc % 8) == 0 && (((uintptr_t)p.C) & 15) == 0;
@@ -710,13 +585,13 @@ extern "C" int mdx_gemm_bf16(const MdxGemmDesc* d, void* stream) {
     // Batched GEMM with a shared A and W batches that are rows of ONE matrix (the per-view V^T projections at levels 1 and 2: 384
     // products of 640 x 350 x 640): run it as a single GEMM over all batches' columns on the XL main loop, the epilogue scattering
     // each column to its batch (GCParams.col_split).  MDX_GEMM_FLATTEN=0 keeps the per-batch launches.
-    const int flatten = (int)opt(OPT_GEMM_FLATTEN);
-    if (flatten && p.batch > 1 && p.sA == 0 && p.sW == (long)p.N * p.ldw && !p.bias && !p.temb && !p.R && !p.epi && !p.c_f32 && p.splitk <= 1 &&
+    const RouteOpts o = route_opts();
+    if (o.GEMM_FLATTEN && p.batch > 1 && p.sA == 0 && p.sW == (long)p.N * p.ldw && !p.bias && !p.temb && !p.R && !p.epi && !p.c_f32 && p.splitk <= 1 &&
         (long)p.batch * p.N < 0x7fffff00L && ((long)p.batch * p.N) % 4 == 0) {
         GCParams q = p;
         q.col_split = p.N; q.N = p.batch * p.N; q.batch = 1; q.sW = 0; q.wide = 0;
-        int rcq = launch_gemm_flat(q, (hipStream_t)stream);
-        if (rcq != MDX_EUNSUPPORTED) return rcq;
+        const Route r = gemm_route_flat(route_in(q, false), o);      // declines (no message) when the XL kernel does not take the shape
+        if (!r.err) return launch_gemm_xl(q, false, r.bn, (hipStream_t)stream);
     }
     return launch_gemm_conv(p, false, (hipStream_t)stream);
 }

@@ -1,7 +1,8 @@
-// gemm_params.h — parameter block and fused epilogue shared by the two GEMM/conv main loops
-// (gemm_conv.hip: register-staged, gemm_dma.hip: LDS-DMA ring).
+// gemm_params.h — parameter block and fused epilogue shared by the GEMM / conv main loops
+// (gemm_conv.hip: register-staged tiles, gemm_ws.hip: weight-stationary, gemm_xl.hip / gemm_xd.hip: 256-row LDS-DMA tiles).
 #pragma once
 #include "common.h"
+#include "gemm_route.h"
 
 namespace mdx {
 
@@ -48,30 +49,16 @@ struct GCParams {
     // "upsampled 2x" conv (MdxConvDesc.upsample2x; gemm_xl.hip only): A is the LOW-RES image batch [upB][Hi][Wi], W holds one [N][2][2][Cin] set per
     // phase, C is the Ho x Wo output (Ho = 2 Hi or 2 Hi - 1); M counts the output pixels.  0 = off.
     int up2, upB;
-    int dbg;                      // debug knobs of gemm_pp.hip (MDX_PP_DBG): 1 skip LDS stores, 2 skip global loads, 4 skip MFMAs
+    int dbg;                      // ablation bits of the launcher's main loop (options WS_DBG / XL_DBG; wrong results)
 };
 
-// Geometry of one phase of the "upsampled 2x" conv (GCParams.up2, include/mdx.h: MdxConvDesc.upsample2x; gemm_xl.hip).  Per axis the output indices fall in
-// classes: 0 even (taps j - 1, j: pad 1), 1 odd (taps j, j + 1: pad 0) and, when n_out = 2 n_in - 1, 2 = the last even index alone (its own
-// weights: the +1 tap of the unfolded conv is zero padding there).  Class c covers `cnt` low-res indices from `first`; output index = 2 j + par.
-struct UpAxis { int cnt, first, pad, par; };
-__host__ __device__ __forceinline__ UpAxis up_axis(int c, int n_in, int n_out) {
-    const int crop = n_out != 2 * n_in;
-    UpAxis a;
-    a.cnt = c == 2 ? 1 : n_in - crop;
-    a.first = c == 2 ? n_in - 1 : 0;
-    a.pad = c == 1 ? 0 : 1;
-    a.par = c == 1 ? 1 : 0;
-    return a;
-}
-// 256-row tiles of all phases (phase = y class * x classes + x class, each phase's tiles contiguous in the M-tile index)
-__host__ __device__ __forceinline__ int up_mtiles(const GCParams& p) {
-    const int ny = 2 + (p.Ho != 2 * p.Hi), nx = 2 + (p.Wo != 2 * p.Wi);
-    int mt = 0;
-    for (int yc = 0; yc < ny; ++yc)
-        for (int xc = 0; xc < nx; ++xc) mt += (int)(((long)p.upB * up_axis(yc, p.Hi, p.Ho).cnt * up_axis(xc, p.Wi, p.Wo).cnt + 255) / 256);
-    return mt;
-}
+// What routing reads of a parameter block (gemm_conv.hip; gemm_route.h holds the predicates and the decision)
+mdx_route::RouteIn route_in(const GCParams& p, bool conv);
+
+// Geometry of the "upsampled 2x" conv (GCParams.up2, include/mdx.h: MdxConvDesc.upsample2x; gemm_xl.hip): gemm_route.h
+using mdx_route::UpAxis;
+using mdx_route::up_axis;
+__host__ __device__ __forceinline__ int up_mtiles(const GCParams& p) { return mdx_route::up_mtiles(p.upB, p.Hi, p.Wi, p.Ho, p.Wo); }
 
 // ---- tile order ------------------------------------------------------------------------
 // 1-D grid -> (M-tile, N-tile).  Workgroup b lands on XCD b % 8 (observed dispatch rule, used for speed only).

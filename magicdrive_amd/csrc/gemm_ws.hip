@@ -543,12 +543,8 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
     ws_wait_vmcnt<0>();                                          // drain the zero-fill tail before the LDS is released
 }
 
-// Whether the weight-stationary kernel can run this problem (the caller decides whether it should).
-bool ws_supported(const GCParams& p) {
-    return p.K == 320 && p.batch <= 1 && p.splitk <= 1 && !p.c_f32 && !p.temb && (p.epi == 0 || p.epi == 1) && (p.N % 4) == 0 &&
-           (p.epi != 1 || (p.N % 64) == 0);
-}
-
+// What the kernel can run / fuse / emit is decided in gemm_route.h (ws_supported, ws_fits_window, ws_fuses_layernorm, ws_emits_rowstat); the launcher
+// below re-checks the three it depends on.
 template <bool GEGLU, bool VT, int LN, bool RS>
 static int launch_ws_one(const GCParams& p, hipStream_t st) {
     constexpr int ST = 3;
@@ -568,27 +564,12 @@ static int launch_ws_one(const GCParams& p, hipStream_t st) {
     const int dbg = (int)opt(OPT_WS_DBG);
     q.dbg = dbg;
     hipLaunchKernelGGL(kern, dim3((unsigned)(nwalk * q.nt)), dim3(256), smem, st, q);
-    return check_launch(GEGLU ? (LN ? "gemm_ws_kernel<geglu,lns>" : "gemm_ws_kernel<geglu>")
-                              : LN == 2 ? (VT ? "gemm_ws_kernel<vT,lns>" : "gemm_ws_kernel<plain,lns>")
-                              : LN == 1 ? (VT ? "gemm_ws_kernel<vT,ln>" : "gemm_ws_kernel<plain,ln>")
-                                        : (VT ? "gemm_ws_kernel<vT>" : RS ? "gemm_ws_kernel<plain,rs>" : "gemm_ws_kernel<plain>"));
+    return check_launch(mdx_route::tag_ws(GEGLU, VT, LN, RS));
 }
 
-// Whether launch_gemm_ws normalises the A rows itself when p.ln_eps > 0 (else the caller must have done it: launch_gemm_conv): plain / V^T epilogues
-// with statistics from the streamed rows or from the producer; GEGLU only with the producer's statistics (MdxGemmDesc.ln_stats).
-bool ws_fuses_layernorm(const GCParams& p) {
-    if (!p.ln_csum || (p.ln_stats && p.ln_stats_parts > 4)) return false;
-    return p.epi == 0 || (p.epi == 1 && p.ln_stats != nullptr);
-}
-// Whether the plain kernel's store phase can emit the row statistics of C (MdxGemmDesc.rowstat_out): 16-byte row walk, one part per 128-column tile.
-bool ws_emits_rowstat(const GCParams& p) {
-    return p.rowstat && p.epi == 0 && !p.Vt && p.wide && !p.c_f32 && p.ln_eps <= 0.f && (p.N + 127) / 128 <= p.rowstat_parts;
-}
-
-// The activation stream reads A through ONE buffer descriptor based at p.A (tile offsets are 32-bit byte offsets into its 2 GiB window, not
-// rebased per tile): the whole extent of A must fit.  launch_gemm_conv asks this before it takes the route — a longer A goes to a main loop
-// that rebases per tile; only the transposed-V form (no other route) is refused below.
-bool ws_fits_window(const GCParams& p) { return (long)p.M * p.lda * 2 < 0x7FFF0000L; }
+static bool ws_fits_window(const GCParams& p) { return mdx_route::ws_fits_window(route_in(p, false)); }
+static bool ws_fuses_layernorm(const GCParams& p) { return mdx_route::ws_fuses_layernorm(route_in(p, false)); }
+static bool ws_emits_rowstat(const GCParams& p) { return mdx_route::ws_emits_rowstat(route_in(p, false)); }
 
 int launch_gemm_ws(const GCParams& p, hipStream_t st) {
     if (!ws_fits_window(p)) return set_error(MDX_EINVAL, "gemm_ws: A exceeds the 2 GiB buffer window (M * lda * 2 = %ld bytes; the transposed-V output has no other main loop)", (long)p.M * p.lda * 2);

@@ -490,17 +490,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 }
 
 // Does the W-direct kernel take this problem?  (q: the GCParams launch_xl prepared — tile order, wide, nblk.)
-bool xd_supported(const GCParams& q) {
-    if (!q.Wq || q.batch > 1 || q.splitk > 1 || q.c_f32 || q.Vt || q.col_split || q.temb || q.rowstat || q.ln_eps > 0.f) return false;
-    if (q.epi != 0 && q.epi != 1) return false;
-    if (q.epi == 1 && (q.R || (q.N % 64))) return false;
-    if ((q.K % 128) || q.K < 640 || (q.N % 16) || !q.wide) return false;
-    if (q.R && ((q.ldr % 8) || ((uintptr_t)q.R & 15))) return false;
-    if (((uintptr_t)q.Wq & 15) || (q.bias && ((uintptr_t)q.bias & 15))) return false;
-    if ((long)256 * q.lda * 2 >= 0x40000000L || (long)256 * q.ldc * 2 >= 0x40000000L || (long)256 * q.ldr * 2 >= 0x40000000L) return false;
-    if ((long)16 * (q.K >> 5) * 1024 >= 0x40000000L) return false;
-    return true;
-}
+bool xd_supported(const GCParams& q) { return mdx_route::xd_supported(route_in(q, false)); }
 
 int launch_gemm_xd(const GCParams& q0, int cus, hipStream_t st) {
     // (today's only caller, launch_xl, sits behind launch_gemm_xl's identical refusal: this one is for a caller that does not)

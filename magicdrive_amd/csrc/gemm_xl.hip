@@ -36,7 +36,7 @@ namespace mdx {
 
 using namespace mdx_xl;
 
-constexpr int XL_SLOTS = 12;                   // distinct temb rows (images) one 256-row tile may span (4x7 images: 11)
+using mdx_route::XL_SLOTS;                     // distinct temb rows (images) one 256-row tile may span (gemm_route.h: xl_supported refuses more)
 
 // Tile order.  swz == 2 ("XCD-blocked panels", round 3; index math in xl_layout.h: raster_tile): the 32 workgroups an XCD runs side
 // by side are ONE panel of gm M-tiles x gn N-tiles, so the operand bytes that XCD's L2 takes in per round of tiles are gm A-panels +
@@ -1430,7 +1430,7 @@ static int launch_xl(const GCParams& p, hipStream_t st) {
                     if (int rc = ensure_dyn_smem((const void*)kp, smem, "xlp")) return rc;
                     hipLaunchKernelGGL(kp, dim3((unsigned)cus), dim3(512), smem, st, q);
                     char tag[96];
-                    snprintf(tag, sizeof tag, "gemm_xlp_kernel<256x256,%s%s>", geglu ? "geglu" : "gemm", has_r ? "+res" : "");
+                    mdx_route::tag_xlp(tag, sizeof tag, geglu, has_r);
                     return check_launch(tag);
                 };
                 if (geglu) return launch_p(gemm_xlp_kernel<true, false>);
@@ -1442,46 +1442,12 @@ static int launch_xl(const GCParams& p, hipStream_t st) {
     }
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, st, q);
     char tag[96];
-    snprintf(tag, sizeof tag, "gemm_xl_kernel<256x%d,%s>", BN, CONV ? (SCHED == 4 ? "conv,kxs" : TAPS == 4 ? "conv,up2x" : "conv") : "gemm");   // (schedules 0-3 are tuning knobs, not part of the name)
+    mdx_route::tag_xl(tag, sizeof tag, BN, CONV, SCHED == 4, TAPS == 4);
     return check_launch(tag);
 }
 
-// Can the XL main loop run this problem at all?  (The caller's cost model decides whether it should.)  bn = 256 or 160.
-bool xl_supported(const GCParams& p, bool conv, int bn) {
-    if (p.batch > 1 || p.splitk > 1 || p.c_f32 || (p.N % 4) || (p.K % 64) || p.Vt) return false;
-    if (p.col_split && (conv || p.bias || p.temb || p.R || p.epi || (p.sC & 1) || (p.ldc & 1) || p.col_split < 16)) return false;
-    if (bn != 256 && bn != 160 && bn != 320) return false;
-    if (p.epi == 1 && (bn != 256 || (p.N % 64))) return false;
-    // SiLU epilogue: only the prologue's map-encoder convs and the time MLP use it (never >= 160 tiles); instantiating it here cost the
-    // 256-wide kernels 17 spilled VGPRs (the residual prefetch went through scratch behind a full vmcnt wait)
-    if (p.epi == 2) return false;
-    if (conv && p.up2) {
-        // upsampled-2x mode: 2x2 phase convs of the low-res input (bias only), 256- or 320-wide tiles; the epilogue's row map divides
-        // (pixel inside the image + 256) through fp32 reciprocals: exact below 2^24
-        // (the K order of the phase weights is the kernel's own: GCParams.cimajor does not apply)
-        if (bn == 160 || p.kh != 2 || p.kw != 2 || (p.Cin % 64) || p.R || p.temb || p.epi || p.col_split) return false;
-        if (p.upB < 1 || p.Hi < 1 || p.Wi < 1 || (p.Ho != 2 * p.Hi && p.Ho != 2 * p.Hi - 1) || (p.Wo != 2 * p.Wi && p.Wo != 2 * p.Wi - 1)) return false;
-        if ((long)p.Hi * p.Wi + 256 >= (1L << 24) || (long)p.upB * p.Hi * p.Wi >= 0x7fffff00L) return false;
-        const long span = ((long)(256 / p.Wi + 3) * p.Wi + 256L + 2 * p.Wi) * p.lda * 2;
-        if (span >= 0x40000000L) return false;
-        // a cropped axis adds edge classes whose grid is one row / column (or one pixel) per image: 256 tile rows then step through up to 256
-        // IMAGES, so the per-lane offsets are bounded only by the whole extent of X (+ the Wi + 1 pixels by which a pad-1 tile's base may lie
-        // before X), which must fit the descriptor's 2 GiB window
-        if ((p.Ho != 2 * p.Hi || p.Wo != 2 * p.Wi) && ((long)p.upB * p.Hi * p.Wi + p.Wi + 2) * p.lda * 2 >= 0x7fff0000L) return false;
-    } else if (conv) {
-        if (p.kh != 3 || p.kw != 3 || p.ph != 1 || p.pw != 1 || (p.Cin % 64) || !p.cimajor) return false;   // pad 1: input pixel index monotonic in m
-        // voffsets are relative to the tile's first receptive-field pixel: 256 output pixels span < 2^31 bytes for every real shape,
-        // but keep the arithmetic honest
-        const long span = ((long)(256 / p.Wo + 3) * p.sh * p.Wi + 256L * p.sw + 3 * p.Wi) * p.lda * 2;
-        if (span >= 0x40000000L) return false;
-    } else if ((long)256 * p.lda * 2 >= 0x40000000L) return false;
-    if ((long)bn * p.ldw * 2 >= 0x40000000L) return false;
-    if (p.temb && p.epi != 1) {
-        const int rows = p.rows_per_b > 0 ? p.rows_per_b : 1;
-        if (256 / rows + 2 > XL_SLOTS) return false;
-    }
-    return true;
-}
+// Can the XL main loop run this problem at all?  (gemm_route.h: the conditions, and the cost model that decides whether it should.)
+bool xl_supported(const GCParams& p, bool conv, int bn) { return mdx_route::xl_supported(route_in(p, conv), bn); }
 
 // MDX_XL_SCHED: 0 (default) = four quadrant phases per slab, refill in the load segments; 1 = two phases per slab with the DMA
 // issued between the MFMAs (measured 10 % slower: the DMA issue lengthens the MFMA segments, which are the serial resource);

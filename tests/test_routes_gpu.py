@@ -412,3 +412,17 @@ def test_xd_fp16_build(dev):
 def test_set_option_rejects_unknown_key():
     with pytest.raises(L.MdxError):
         L.set_option("NO_SUCH_SWITCH", 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The route table (tests/golden/gemm_routes.json, recorded by tools/route_table.py from the library before routing moved into csrc/gemm_route.h):
+# every threshold of the routing decision, one launch per case, asserted through mdx_last_kernel().
+import gemm_route_table as RT  # noqa: E402
+
+ROUTE_CASES = [c for c in RT.load() if c["gpu"]]
+
+
+@pytest.mark.parametrize("c", ROUTE_CASES, ids=[c["name"] for c in ROUTE_CASES])
+def test_route_table(dev, c):
+    tag, _ = RT.run_case(c)
+    assert tag == c["tag"], (c["name"], tag, c["tag"])
