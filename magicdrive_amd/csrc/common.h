@@ -67,21 +67,7 @@ __device__ __forceinline__ float silu_f(float x) { return x * __frcp_rn(1.0f + _
 // programme on 3000 points, tools/fit_erf.py): |error| <= 2.7e-5 in fp32 Horner arithmetic — 150x below the bf16 rounding of the
 // product it feeds (2^-9 relative).  14 full-rate VALU operations and NO transcendental: the GEGLU epilogue of the level-0 feed-forward
 // evaluates 1.4 G of these per launch and was VALU-bound on the round-2 form (Abramowitz-Stegun 7.1.26: 13 operations + v_rcp_f32 +
-// v_exp_f32 at quarter rate = 21 issue slots; profiles/README.md round 3).  -DMDX_GELU_AS selects the old form (A/B side builds).
-#ifdef MDX_GELU_AS
-__device__ __forceinline__ float erf_as_f(float x) {
-    const float ax = fabsf(x);
-    const float t = __frcp_rn(1.0f + 0.3275911f * ax);
-    float poly = 1.061405429f;
-    poly = poly * t - 1.453152027f;
-    poly = poly * t + 1.421413741f;
-    poly = poly * t - 0.284496736f;
-    poly = poly * t + 0.254829592f;
-    const float y = 1.0f - poly * t * __expf(-ax * ax);
-    return copysignf(y, x);
-}
-__device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f + erf_as_f(x * 0.70710678118654752440f)); }
-#else
+// v_exp_f32 at quarter rate = 21 issue slots; profiles/README.md round 3).
 __device__ __forceinline__ float erf_poly_f(float z) {
     const float zc = __builtin_amdgcn_fmed3f(z, -3.0f, 3.0f);
     const float u = zc * zc;
@@ -100,18 +86,12 @@ __device__ __forceinline__ float gelu_erf_f(float x) {
     const float hx = 0.5f * x;
     return __builtin_fmaf(hx, erf_poly_f(x * 0.70710678118654752440f), hx);
 }
-#endif
 
 // Two GELUs at once on packed fp32 (v_pk_mul_f32 / v_pk_fma_f32: one instruction, two lanes' worth of elements each): 15 instructions per PAIR (two
 // clamps + 13 packed) instead of 2 x 14 — the GEGLU epilogues evaluate 1.4 G of these per level-0 launch and are VALU-bound (profiles/README.md round 3).
-// Same polynomial, same operation order per element as gelu_erf_f: bit-identical results.  -DMDX_GELU_PK=0 keeps the scalar form (A/B side builds).
-#ifndef MDX_GELU_PK
-#define MDX_GELU_PK 1
-#endif
+// Same polynomial, same operation order per element as gelu_erf_f: bit-identical results (the scalar pair measured 0.4-1.0 % slower: profiles/r05_gelu_pk_ab.log).
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-#ifndef MDX_GELU_AS
 __device__ __forceinline__ f32x2_t gelu_erf_f2(f32x2_t x) {
-#if MDX_GELU_PK
     const f32x2_t z = x * 0.70710678118654752440f;
     f32x2_t zc;
     zc.x = __builtin_amdgcn_fmed3f(z.x, -3.0f, 3.0f); zc.y = __builtin_amdgcn_fmed3f(z.y, -3.0f, 3.0f);
@@ -129,13 +109,7 @@ __device__ __forceinline__ f32x2_t gelu_erf_f2(f32x2_t x) {
     const f32x2_t e = zc * p;
     const f32x2_t hx = x * 0.5f;
     return __builtin_elementwise_fma(hx, e, hx);
-#else
-    return f32x2_t{gelu_erf_f(x.x), gelu_erf_f(x.y)};
-#endif
 }
-#else
-__device__ __forceinline__ f32x2_t gelu_erf_f2(f32x2_t x) { return f32x2_t{gelu_erf_f(x.x), gelu_erf_f(x.y)}; }
-#endif
 
 // Two 16-bit products + fp32 accumulate in one instruction (v_dot2_f32_bf16 / v_dot2_f32_f16), no unpacking: a and b hold two values of the
 // build's 16-bit type each.  The products are exact in fp32.

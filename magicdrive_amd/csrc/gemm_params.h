@@ -49,7 +49,6 @@ struct GCParams {
     // "upsampled 2x" conv (MdxConvDesc.upsample2x; gemm_xl.hip only): A is the LOW-RES image batch [upB][Hi][Wi], W holds one [N][2][2][Cin] set per
     // phase, C is the Ho x Wo output (Ho = 2 Hi or 2 Hi - 1); M counts the output pixels.  0 = off.
     int up2, upB;
-    int dbg;                      // ablation bits of the launcher's main loop (options WS_DBG / XL_DBG; wrong results)
 };
 
 // What routing reads of a parameter block (gemm_conv.hip; gemm_route.h holds the predicates and the decision)

@@ -299,8 +299,8 @@ inline Route gemm_route(RouteIn p, const RouteOpts& o) {
 inline void tag_generic(char* s, size_t n, int BM, int BN, int BK, bool conv) {
     snprintf(s, n, "gemm_conv_kernel<%d,%d,%d,%d,%d,%s>", BM, BN, BK, BM == 256 ? 4 : 2, 2, conv ? "conv" : "gemm");
 }
-inline void tag_xl(char* s, size_t n, int bn, bool conv, bool kxs, bool up2) {   // (schedules 0-3 are tuning knobs, not part of the name)
-    snprintf(s, n, "gemm_xl_kernel<256x%d,%s>", bn, conv ? (kxs ? "conv,kxs" : up2 ? "conv,up2x" : "conv") : "gemm");
+inline void tag_xl(char* s, size_t n, int bn, bool conv, bool up2) {
+    snprintf(s, n, "gemm_xl_kernel<256x%d,%s>", bn, conv ? (up2 ? "conv,up2x" : "conv") : "gemm");
 }
 inline void tag_xlp(char* s, size_t n, bool geglu, bool has_r) {
     snprintf(s, n, "gemm_xlp_kernel<256x256,%s%s>", geglu ? "geglu" : "gemm", has_r ? "+res" : "");
@@ -314,7 +314,7 @@ inline const char* tag_ws(bool geglu, bool vt, int ln, bool rs) {
 }
 // Tag of the main launch of a route (an XL GEMM may run in its persistent form: that choice is launch_xl's).
 inline void route_tag(const Route& r, const RouteIn& p, char* s, size_t n) {
-    if (r.main == MAIN_XL) tag_xl(s, n, r.bn, p.conv, false, p.up2);
+    if (r.main == MAIN_XL) tag_xl(s, n, r.bn, p.conv, p.up2);
     else if (r.main == MAIN_GENERIC) tag_generic(s, n, r.BM, r.BN, r.BK, p.conv);
     else snprintf(s, n, "%s", tag_ws(p.epi == 1, false, !r.keep_ln ? 0 : r.keep_ln_stats ? 2 : 1, r.keep_rowstat));
 }

@@ -66,7 +66,7 @@ __device__ __forceinline__ void ws_lds_barrier() {
 // product into rstd_m acc + (-mean_m rstd_m) csum_n + bias_n.  gamma / beta are in W / bias (packed by the host).  The tokens are
 // read ONCE (by this GEMM) instead of read + written by layernorm_kernel and read again here.  One-pass variance in fp32
 // (E[x^2] - mean^2 over 320 values of a 16-bit tensor).  Every N-tile's workgroup repeats the row sums, and they are NOT free: measured
-// (tools/lnone.py, 768 views, side builds -DMDX_WS_LN_ABLATE) the fused q/k/v launch pair is 150 us slower than the plain one (1200 us) —
+// (tools/lnone.py, 768 views; side builds that dropped the sums / the extra read, profiles/README.md round 3) the fused q/k/v launch pair is 150 us slower than the plain one (1200 us) —
 // 100 us the 96 VALU operations per slab (each costs its 4-cycle issue slot whether it sits in front of the slab's MFMAs or between
 // them), 15 us the extra fragment read, 35 us the epilogue — against the 240-400 us LayerNorm pass it replaces; to_q: +105 us.  For
 // the GEGLU (20 N-tiles, a VALU-heavy epilogue already) the same scheme cost +485 us per launch, more than the pass: not built
@@ -213,14 +213,6 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
     const bf16_t* Rg = p.R ? (const bf16_t*)p.R : nullptr;
     bf16_t* Cg = (bf16_t*)p.C;
     constexpr bool vtile = VT;
-    // Ablations (WS_DBG: 1 GEGLU without GELU, 2 main loop only, 4 no MFMAs) exist only in -DMDX_WS_ABLATE builds: as runtime tests they
-    // sat INSIDE the slab loop — one scalar branch per k-step, which cut the loop into 20 basic blocks of {4 fragment reads, wait, 4 MFMAs}
-    // per tile and kept the compiler from reading a slab's fragments ahead of its MFMAs (seen in the .s; round 3).
-#ifdef MDX_WS_ABLATE
-    const bool do_mma = !(p.dbg & 4), no_gelu = p.dbg & 1, no_epi = p.dbg & 2;
-#else
-    constexpr bool do_mma = true, no_gelu = false, no_epi = false;
-#endif
     const int n0o = GEGLU ? n0 / 2 : n0, Nout = GEGLU ? p.N / 2 : p.N;
     int q = 0;                                                   // slab counter (ring stage = q % ST)
     float s1a = 0.f, s1b = 0.f, s2a = 0.f, s2b = 0.f;            // LN: sums of x / x^2 of row 32 wave + frow over this lane's half of the k chunks
@@ -277,11 +269,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
             // between its 4 MFMAs, 6 behind each.
             Frag8 sf[2];
             const unsigned char* sr = as + wave * (32 * 128);
-#if defined(MDX_WS_LN_ABLATE) && (MDX_WS_LN_ABLATE & 2)              // ... and the read too (one per tile keeps the code shape)
-            if constexpr (LN == 1) { if (s == 0) sf[0].u = *(const uint4*)(sr + (x0 << 4)); }
-#else
             if constexpr (LN == 1) sf[0].u = *(const uint4*)(sr + (x0 << 4));
-#endif
 #pragma unroll
             for (int i = 0; i < 4; ++i) af[0][i].u = *(const uint4*)(as + i * 32 * 128 + (x0 << 4));
             if constexpr (LN == 1) __builtin_amdgcn_sched_barrier(0); else __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
@@ -289,11 +277,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
             for (int ks = 0; ks < 4; ++ks) {
                 if (ks + 1 < 4) {
                     const int co = (x0 ^ ((ks + 1) << 1)) << 4;
-#if defined(MDX_WS_LN_ABLATE) && (MDX_WS_LN_ABLATE & 2)
-                    if constexpr (LN == 1) sf[(ks + 1) & 1].u = sf[ks & 1].u;
-#else
                     if constexpr (LN == 1) sf[(ks + 1) & 1].u = *(const uint4*)(sr + co);
-#endif
 #pragma unroll
                     for (int i = 0; i < 4; ++i) af[(ks + 1) & 1][i].u = *(const uint4*)(as + i * 32 * 128 + co);
                 }
@@ -304,33 +288,25 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
                     if (ks + 1 < 4) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        if (do_mma) {
-                            if (vtile) acc[i] = MDX_MFMA_32x32x16(af[ks & 1][i].v, wf[s * 4 + ks].v, acc[i]);
-                            else acc[i] = MDX_MFMA_32x32x16(wf[s * 4 + ks].v, af[ks & 1][i].v, acc[i]);
-                        }
-#if defined(MDX_WS_LN_ABLATE) && (MDX_WS_LN_ABLATE & 1)      // side builds (tools/lnone.py): drop the sums, keep the extra fragment read
-                        if (i == 0) s1a += bf2f(sf[ks & 1].h[0]);
-#else
+                        if (vtile) acc[i] = MDX_MFMA_32x32x16(af[ks & 1][i].v, wf[s * 4 + ks].v, acc[i]);
+                        else acc[i] = MDX_MFMA_32x32x16(wf[s * 4 + ks].v, af[ks & 1][i].v, acc[i]);
                         const float xa = bf2f(sf[ks & 1].h[2 * i]), xb = bf2f(sf[ks & 1].h[2 * i + 1]);
                         s1a += xa; s1b += xb;
                         s2a = __builtin_fmaf(xa, xa, s2a); s2b = __builtin_fmaf(xb, xb, s2b);
-#endif
                         // (the empty asm ties the sums to this point: instruction selection orders only side-effecting nodes against the fence)
                         asm volatile("" : "+v"(s1a), "+v"(s1b), "+v"(s2a), "+v"(s2b));
                         __builtin_amdgcn_sched_barrier(0);
                     }
                     continue;
                 }
-                if (do_mma) {
-                    if (vtile) {          // operands swapped: the accumulator comes out transposed (lane = channel, registers = tokens)
+                if (vtile) {              // operands swapped: the accumulator comes out transposed (lane = channel, registers = tokens)
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            acc[i] = MDX_MFMA_32x32x16(af[ks & 1][i].v, wf[s * 4 + ks].v, acc[i]);
-                    } else {
+                    for (int i = 0; i < 4; ++i)
+                        acc[i] = MDX_MFMA_32x32x16(af[ks & 1][i].v, wf[s * 4 + ks].v, acc[i]);
+                } else {
 #pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            acc[i] = MDX_MFMA_32x32x16(wf[s * 4 + ks].v, af[ks & 1][i].v, acc[i]);
-                    }
+                    for (int i = 0; i < 4; ++i)
+                        acc[i] = MDX_MFMA_32x32x16(wf[s * 4 + ks].v, af[ks & 1][i].v, acc[i]);
                 }
                 // pin the order {fragment reads of k-step ks + 1} {4 MFMAs of k-step ks}: the machine scheduler otherwise sinks the
                 // reads back next to their use to save registers
@@ -342,7 +318,6 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
             if constexpr (LN == 1) asm volatile("" : "+v"(s1a), "+v"(s1b), "+v"(s2a), "+v"(s2b));
         }
         // ---- epilogue of tile t: staging is separate from the ring, which keeps streaming ----
-        if (no_epi) continue;                                    // ablation: main loop only
         if constexpr (LN == 1) {
             float s1 = s1a + s1b, s2 = s2a + s2b;
             s1 += __shfl_xor(s1, 32, 64); s2 += __shfl_xor(s2, 32, 64);          // the other half of the k chunks
@@ -432,7 +407,7 @@ __global__ __launch_bounds__(256, 2) void gemm_ws_kernel(GCParams p) {
                                 x0 = acc[i][4 * g + e] + bvv[e]; x1 = acc[i][4 * g + e + 1] + bvv[e + 1];
                                 gt.x = acc[i][8 + 4 * g + e] + bgg[e]; gt.y = acc[i][8 + 4 * g + e + 1] + bgg[e + 1];
                             }
-                            const f32x2_t ge = no_gelu ? gt : gelu_erf_f2(gt);
+                            const f32x2_t ge = gelu_erf_f2(gt);
                             o[e] = x0 * ge.x; o[e + 1] = x1 * ge.y;
                         }
                         uint2 ov; ov.x = pack2bf(o[0], o[1]); ov.y = pack2bf(o[2], o[3]);
@@ -561,8 +536,6 @@ static int launch_ws_one(const GCParams& p, hipStream_t st) {
     const int mt8 = (q.mt + 7) / 8 * 8;
     if (nwalk > mt8) nwalk = mt8;
     q.swz = nwalk;
-    const int dbg = (int)opt(OPT_WS_DBG);
-    q.dbg = dbg;
     hipLaunchKernelGGL(kern, dim3((unsigned)(nwalk * q.nt)), dim3(256), smem, st, q);
     return check_launch(mdx_route::tag_ws(GEGLU, VT, LN, RS));
 }

@@ -1,9 +1,11 @@
-// gemm_xl.hip — the large-shape bf16 MFMA GEMM / implicit-GEMM convolution main loop for gfx950: 256 x {256,160} x 64 tiles,
-// operands global -> LDS by LDS-DMA, quadrant phases, counted vmcnt, two wave groups staggered by one barrier.
+// gemm_xl.hip — the large-shape bf16 MFMA GEMM / implicit-GEMM convolution main loop for gfx950: 256 x {320,256,160} x 64 tiles,
+// operands global -> LDS by LDS-DMA, quadrant phases, counted vmcnt, two wave groups staggered by one barrier.  Two kernels:
+// gemm_xl_kernel<BN, CONV, TAPS> (one tile per workgroup; ONE main-loop schedule per tile width: the 320-wide quadrant order, and the
+// four-phase order below for 256 / 160 wide) and gemm_xlp_kernel (the persistent 256-wide GEMM: one workgroup per CU walks the tiles).
 //
-// Why a third main loop (after gemm_conv.hip's 128x128 register-staged tile and gemm_pp.hip's register-staged ping-pong):
-// round 1 measured both as bound by the global -> register -> LDS staging path (profiles/README.md: ~32 B/clk per CU, a load phase
-// of 1.2-1.7 k cycles beside 1.0 k cycles of MFMA issue).  Here nothing is staged through registers:
+// Why this main loop beside gemm_conv.hip's 128x128 register-staged tile: round 1 measured register staging as bound by the
+// global -> register -> LDS path (profiles/README.md: ~32 B/clk per CU, a load phase of 1.2-1.7 k cycles beside 1.0 k cycles of
+// MFMA issue).  Here nothing is staged through registers:
 //   * every operand byte goes global -> LDS with `buffer_load_dwordx4 ... lds` (1 KiB per wave instruction, full 128-byte lines per
 //     row), the XOR swizzle that makes the ds_read_b128 fragment reads conflict-free is applied on the SOURCE address
 //     (xl_layout.h); conv zero padding / row tails are lanes whose voffset is out of the descriptor's range (the DMA writes zeros);
@@ -19,7 +21,7 @@
 //
 // Epilogue: bias (+ the per-(step, image) temb row) staged once per tile as fp32 addend rows in LDS; applied in registers with
 // SiLU / GEGLU; the bf16 tile is transposed through LDS (whole 256-row tile at once: the operand ring is dead) and written as
-// 16-byte row segments with the residual added — same arithmetic per element as gemm_conv.hip / gemm_pp.hip.
+// 16-byte row segments with the residual added — same arithmetic per element as gemm_conv.hip.
 //
 // Replaces (through mdx_gemm_bf16 / mdx_conv2d_bf16, include/mdx.h): ATen addmm / conv2d of ResnetBlock2D (resnet.py:590-640),
 // Down/Upsample2D convs (resnet.py:165-170, 198-222), the transformer projections and feed-forward (attention.py:200-280,
@@ -58,32 +60,17 @@ __device__ __forceinline__ int xl_div24(int n, int d, float rd) {
 
 // TAPS: K slabs per 64-channel block of a conv: 9 = the 3x3 / pad 1 conv; 4 = one 2x2 phase conv of the upsampled-2x mode (the tile index selects
 // the phase: its weight set, its padding and the strided rows of Y it stores).
-template <int BN, bool CONV, int SCHED, int TAPS = 9>
+template <int BN, bool CONV, int TAPS = 9>
 __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     using G = Geo<BN>;
     constexpr bool UP = CONV && TAPS == 4;
     constexpr int KW = UP ? 2 : 3;
-    static_assert(TAPS == 9 || (TAPS == 4 && CONV && SCHED == 0), "tap counts: 9 (3x3) or 4 (2x2 phase of the upsampled-2x conv)");
+    static_assert(TAPS == 9 || (TAPS == 4 && CONV), "tap counts: 9 (3x3) or 4 (2x2 phase of the upsampled-2x conv)");
     constexpr int BM = 256, NTH = 512;
     constexpr int TI = G::TI, TJ = G::TJ, TJ0 = G::TJ0, TJ1 = TJ - TJ0, TIH = TI / 2;
     constexpr int A_BYTES = BM * 128, B_BYTES = G::BNP * 128, BUF = A_BYTES + B_BYTES;
     constexpr int PA = G::PA, PB0 = G::PB0, PB1 = G::PB1;
     constexpr int UNIT_MAX = PA > PB0 ? PA : PB0;
-    // SCHED 4 (round 6, 320-wide 3x3 / stride 1 / pad 1 convs): the three HORIZONTAL taps of a (channel block, ky) share ONE A slab.  In the
-    // flattened pixel order tap kx of output pixel m reads input pixel m + (ky - 1) W + (kx - 1): the slab of tap kx = 0 shifted by kx rows.  So the
-    // A region holds 258 rows — LDS row r = input pixel m0 - 1 + r (+ the ky row shift) — loaded once per group of three K slabs (two 272-row A
-    // buffers alternating by group, the 40 KB weight slabs still alternate by slab), and the fragment reads of tap kx start kx rows further
-    // down.  The left / right image border, where the flattened neighbour is a pixel of the next image row, is a per-lane select of the fragment
-    // address: border lanes read a zero row.  Operand bytes into the CU per channel block: 3 x 34 + 9 x 40 KB instead of 9 x 72 (-29 %) — the lever
-    // the round-4/6 ablations point at (zero-filling the A pieces of kx = 1, 2 without touching the instruction stream: +6...8 %,
-    // profiles/r06_xl_a_bytes_ablation.log).  The row swizzle of this A region is row & 7 (conflict-free ds_read_b128 for row shifts 0, 1, 2;
-    // the (row >> 1) & 7 rule of the other regions pairs even / odd rows and collides 2-way under an odd shift: tests/xl_layout_check.cpp).
-    constexpr bool KXS = SCHED == 4;
-    static_assert(!KXS || (BN == 320 && CONV), "the shared-tap schedule is the 320-wide conv's");
-    constexpr int AS_ROWS = 272, AS_BYTES = AS_ROWS * 128;       // 256 + 2 halo rows (+ 6 of their piece) + 8 zero rows (the dummy pieces' target, the border select's source)
-    constexpr int ZROW_OFF = 264 * 128;
-    constexpr int B_STRIDE = KXS ? (G::BNP * 128) : (BM * 128 + G::BNP * 128);      // SCHED 4: [A buf 0 | A buf 1 | B buf 0 | B buf 1]; else [A | B] x 2
-    constexpr int B_BASE = KXS ? 2 * AS_BYTES - BM * 128 : 0;                        // (b_lds / b_rd carry the A_BYTES of the interleaved layout)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -140,14 +127,11 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     const xl_rsrc_t rsB = xl_make_rsrc(Wb + (long)n0 * p.ldw);
     const unsigned lds0 = (unsigned)(unsigned long long)(lds_void_t*)smem;      // LDS byte address of the dynamic region
 
-    // SCHED 4 keeps its per-lane state in TWO registers (the 320-wide kernel has none to spare: 160 accumulators + 56 fragment registers):
-    //   xs_bits  bits 3 (2 h + e) + ky: LDS row of piece (h, e) exists for row shift ky - 1;  12 + ky: the halo piece's;  16 + i / 24 + i: MFMA row
-    //            tile i of this lane sits on the left / right image border
-    //   xs_vb    byte offset of this lane's 16 bytes inside ANY A piece: (lane >> 3) rows + the chunk ((lane & 7) ^ (row & 7)) — piece rows start at
-    //            multiples of 8, so the swizzle does not depend on the piece; the piece's first row is added as a scalar at issue time
-    unsigned xs_bits = 0;
-    const unsigned xs_vb = (unsigned)((long)(lane >> 3) * p.lda * 2 + (((lane & 7) ^ ((lane >> 3) & 7)) << 4));
-    const unsigned xb_vb = (unsigned)((long)(lane >> 3) * p.ldw * 2 + (((lane & 7) ^ ((lane >> 4) & 3)) << 4));     // (row >> 1) & 7 of rows 0..7
+    // No effect on the result: the swizzled chunk of this lane for piece rows 0..7, which the loops below form again.  WHERE it is first formed
+    // decides the order of the bookkeeping's instructions and, through the scheduler's tie-breaks, the scalar register allocation of the whole
+    // kernel.  It is formed here, where the retired shared-tap schedule formed it, so that every instantiation stays instruction-identical to
+    // commit 9d4c44c (profiles/retire_variants_isa.log); drop the line the next time this kernel's code changes anyway.
+    [[maybe_unused]] const int lane_chunk0 = (lane & 7) ^ ((lane >> 4) & 3);
     unsigned a_voff[2][PA];                                      // [unit A0 / A1][piece]
     unsigned a_taps[2][PA];                                      // CONV: bit t set = tap t reads inside the image (else zero)
     int a_lds[2][PA];                                            // LDS byte offset of the piece inside a buffer (wave-uniform)
@@ -161,18 +145,6 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
             const int cl = piece_lane_chunk(row0, lane);
             const int m = m0 + R;
             a_taps[h][e] = 0;
-            if constexpr (KXS) {
-                // LDS row R = input pixel q = m0 - 1 + R of the centre image row (the ky shift rides in the scalar offset): bit ky = q exists and
-                // its row y + ky - 1 is inside the image (the x position is the pixel's own: always inside)
-                const long q = (long)m0 + R - 1;
-                unsigned bits = 0;
-                if (q >= 0 && q < p.M) {
-                    const int b_ = (int)(q / hw), y_ = (int)(q - (long)b_ * hw) / Wo;
-#pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) if ((unsigned)(y_ + ky - 1) < (unsigned)p.Hi) bits |= 1u << ky;
-                }
-                xs_bits |= bits << (3 * (2 * h + e));             // (a_voff / a_taps stay unused: ONE base offset + the piece's wave-uniform row offset, XS_PIECE_A)
-            } else
             if (CONV) {
                 const int mm = min(m, M_ - 1);
                 const int b = mm / hw, rem = mm - b * hw;
@@ -209,16 +181,6 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
             }
         }
 
-    // SCHED 4: the slab's rows 256, 257 (+ 6 zero-filled rows of their piece) come from wave 7; the other waves' extra piece zero-fills rows 264-271
-    if constexpr (KXS) {
-        const int R = 256 + (lane >> 3);
-        const long q = (long)m0 + R - 1;
-        if (wave == 7 && R < 258 && q < p.M) {
-            const int b_ = (int)(q / hw), y_ = (int)(q - (long)b_ * hw) / Wo;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) if ((unsigned)(y_ + ky - 1) < (unsigned)p.Hi) xs_bits |= 1u << (12 + ky);
-        }
-    }
     // slab T -> scalar byte offsets of its k position in A and W
     const int row_bytes = (int)(p.lda * 2);
     auto a_soff = [&](int T, int& tap) -> int {
@@ -238,83 +200,30 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
         }
         return T * 128;
     };
-    // Debug ablations (XL_DBG: 1 skip the MFMAs, 2 skip the DMA, 4 return after the main loop, 8 stage C but store nothing) exist only in builds with -DMDX_XL_ABLATE: a runtime test inside
-    // the MFMA clusters splits their scheduling regions.
-#ifdef MDX_XL_ABLATE
-    const bool do_mma = !(p.dbg & 1), do_dma = !(p.dbg & 2);
-    // round 6, the price of the 3x3 conv's nine A fetches per channel block (what a shared input halo would save): 16 = the A pieces of taps 1..8 are
-    // issued with out-of-range offsets (zero fill: same instruction stream, none of their bytes enter the CU); 32 = they are not issued at all
-    // (the hand-counted waits then cover less than they should: timing only, an optimistic bound)
-    const bool a_oob = CONV && (p.dbg & 16), a_skip = CONV && (p.dbg & 32);
-    const bool a_oob_kx = CONV && (p.dbg & 64);                   // 64 = zero fill only for kx != 0 (what sharing a row's three horizontal taps would save)
-#else
-    constexpr bool do_mma = true, do_dma = true, a_oob = false, a_skip = false, a_oob_kx = false;
-#endif
     // ONE 1-KiB piece (e) of a load unit of slab T into buffer T & 1; nothing past the last slab (the waits account for it)
 #define XL_PIECE_A(h, e, T)                                                                                                       \
     if constexpr ((e) < PA) {                                                                                                     \
-        if ((T) < nt && do_dma && !(a_skip && ((T) % 9) != 0)) {                                                                  \
+        if ((T) < nt) {                                                                                                           \
             int tap_;                                                                                                             \
             const int so_ = a_soff((T), tap_);                                                                                    \
-            unsigned vo_ = CONV ? (((a_taps[h][(e) < PA ? (e) : 0] >> tap_) & 1u) ? a_voff[h][(e) < PA ? (e) : 0] : XL_OOB)       \
-                                : a_voff[h][(e) < PA ? (e) : 0];                                                                  \
-            if ((a_oob && tap_ != 0) || (a_oob_kx && (tap_ % 3) != 0)) vo_ = XL_OOB;                                              \
+            const unsigned vo_ = CONV ? (((a_taps[h][(e) < PA ? (e) : 0] >> tap_) & 1u) ? a_voff[h][(e) < PA ? (e) : 0] : XL_OOB) \
+                                      : a_voff[h][(e) < PA ? (e) : 0];                                                            \
             xl_glds(rsA, lds0 + ((T) & 1) * BUF + a_lds[h][(e) < PA ? (e) : 0], vo_, so_);                                        \
         }                                                                                                                         \
     }
 #define XL_PIECE_B(part, e, T)                                                                                                    \
     if constexpr ((e) < ((part) ? PB1 : PB0)) {                                                                                   \
-        if ((T) < nt && do_dma)                                                                                                   \
-            xl_glds_b(rsB, lds0 + ((T) & 1) * B_STRIDE + B_BASE + b_lds[part][(e) < UNIT_MAX ? (e) : 0],                            \
+        if ((T) < nt)                                                                                                             \
+            xl_glds_b(rsB, lds0 + ((T) & 1) * BUF + b_lds[part][(e) < UNIT_MAX ? (e) : 0],                                        \
                       b_voff[part][(e) < UNIT_MAX ? (e) : 0], b_soff((T)));                                                       \
     }
 #define XL_ISSUE_A(h, T) { XL_PIECE_A(h, 0, T) XL_PIECE_A(h, 1, T) }
-    // SCHED 4: unit h of the shared A slab of GROUP G = (channel block, ky) into A buffer G & 1; xs_ky / xs_so = ky and scalar offset of that group
-#define XS_PIECE_A(h, e, G)                                                                                                       \
-    if ((G) < ng && do_dma) {                                                                                                     \
-        unsigned va_ = xs_vb;                                                                                                     \
-        asm volatile("" : "+v"(va_));                                                                                             \
-        const unsigned vo_ = va_ + (unsigned)((a_lds[h][e] >> 7) * row_bytes);                                                    \
-        xl_glds(rsA, lds0 + ((G) & 1) * AS_BYTES + a_lds[h][e], ((xs_bits >> (3 * (2 * (h) + (e)) + xs_ky)) & 1u) ? vo_ : XL_OOB, xs_so); \
-    }
-    // B pieces of SCHED 4 from ONE per-lane register too (N % 320 == 0: no column tail): piece rows start at multiples of 8, so only the parity of
-    // row0 / 8 enters the (row >> 1) & 7 swizzle — bit 2 of the chunk = bit 6 of the byte offset (ldw * 2 is a multiple of 128)
-#define XS_PIECE_B(part, e, T)                                                                                                    \
-    if constexpr ((e) < ((part) ? PB1 : PB0)) {                                                                                   \
-        if ((T) < nt && do_dma) {                                                                                                 \
-            const int r0_ = (b_lds[part][(e) < UNIT_MAX ? (e) : 0] - A_BYTES) >> 7;                                               \
-            unsigned vb_ = xb_vb;                                                                                                 \
-            asm volatile("" : "+v"(vb_));   /* formed HERE: as loop invariants the five offsets are hoisted and then spilled (scratch reloads + vmcnt(0) in the loop) */ \
-            const unsigned vo_ = (vb_ ^ (unsigned)(((r0_ >> 3) & 1) << 6)) + (unsigned)(r0_ * (int)(p.ldw * 2));                  \
-            xl_glds_b(rsB, lds0 + ((T) & 1) * B_STRIDE + B_BASE + b_lds[part][(e) < UNIT_MAX ? (e) : 0], vo_, b_soff((T)));        \
-        }                                                                                                                         \
-    }
-#define XS_ISSUE_B(part, T) { XS_PIECE_B(part, 0, T) XS_PIECE_B(part, 1, T) XS_PIECE_B(part, 2, T) }
-#define XS_ISSUE_A0(G) { XS_PIECE_A(0, 0, G) XS_PIECE_A(0, 1, G) }
-#define XS_ISSUE_A1X(G)                                                                                                           \
-    {                                                                                                                             \
-        XS_PIECE_A(1, 0, G) XS_PIECE_A(1, 1, G)                                                                                   \
-        unsigned va2_ = xs_vb;                                                                                                    \
-        asm volatile("" : "+v"(va2_));                                                                                            \
-        if ((G) < ng && do_dma)                                                                                                   \
-            xl_glds(rsA, lds0 + ((G) & 1) * AS_BYTES + (wave == 7 ? 256 * 128 : ZROW_OFF),                                        \
-                    ((xs_bits >> (12 + xs_ky)) & 1u) ? va2_ + (unsigned)(256 * row_bytes) : XL_OOB, xs_so);                       \
-    }
 #define XL_ISSUE_B(part, T) { XL_PIECE_B(part, 0, T) XL_PIECE_B(part, 1, T) XL_PIECE_B(part, 2, T) }
 
     // ---- fragment read offsets (bytes inside a buffer) ----
     const int fo0 = frag_off(0, lane, 0), fo1 = frag_off(0, lane, 1);     // row part = (lane & 15) * 128: tile row blocks add multiples of 2048
     const int a_rd = a_tile_row0<BN>(wm, 0) * 128;
     const int b_rd = A_BYTES + b_tile_row0<BN>(wn, 0) * 128;
-    if constexpr (KXS) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i) {
-            const int m_ = m0 + a_tile_row0<BN>(wm, i) + (lane & 15);
-            const int ox_ = m_ % Wo;                              // (rows past M: their outputs are never stored)
-            if (ox_ == 0) xs_bits |= 1u << (16 + i);
-            if (ox_ == Wo - 1) xs_bits |= 1u << (24 + i);
-        }
-    }
 
     f32x4_t acc[TI][TJ];
 #pragma unroll
@@ -334,80 +243,24 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
             af[i][1].u = *(const uint4*)(s_ + i * 2048 + fo1);                                                                    \
         }                                                                                                                         \
     }
-    // SCHED 4: A half h of the shared slab in A buffer ab_, tap kx_ (rows shifted by kx_); lanes whose output pixel sits on the left (kx 0) / right
-    // (kx 2) image border read the zero row instead (xs_lb / xs_rb: bit i = MFMA row tile i of this lane is on that border)
-#define XS_READ_A(h, ab_)                                                                                                         \
+    // B tiles J0 .. J0 + NJ - 1 of the wave into fragment registers D0 .. (D0 = J0 except on the 320-wide tile, whose B1 tiles reuse B0's registers)
+#define XL_READ_B(D0, J0, NJ, buf_)                                                                                               \
     {                                                                                                                             \
-        const unsigned char* s_ = smem + (ab_) * AS_BYTES;                                                                        \
-        unsigned bb_ = xs_bsel;                                                                                                   \
-        asm volatile("" : "+v"(bb_));   /* the selects are formed HERE: hoisted out of the loop they are 48 live values (seen as scratch reloads inside the slab loop) */ \
-        const int f0_ = xs_f0, f1_ = xs_f0 ^ 64;                                                                                  \
-        _Pragma("unroll") for (int i = 0; i < TIH; ++i) {                                                                         \
-            const int it_ = (h) * TIH + i;                                                                                        \
-            const bool z_ = (bb_ >> it_) & 1u;                                                                                    \
-            const int o0_ = z_ ? ZROW_OFF - it_ * 2048 : f0_, o1_ = z_ ? ZROW_OFF - it_ * 2048 : f1_;                             \
-            af[i][0].u = *(const uint4*)(s_ + o0_ + it_ * 2048);                                                                  \
-            af[i][1].u = *(const uint4*)(s_ + o1_ + it_ * 2048);                                                                  \
-        }                                                                                                                         \
-    }
-#define XL_READ_B(J0, NJ, buf_)                                                                                                   \
-    {                                                                                                                             \
-        const unsigned char* s_ = smem + (buf_) * B_STRIDE + B_BASE + b_rd;                                                       \
-        _Pragma("unroll") for (int j = (J0); j < (J0) + (NJ); ++j) {                                                              \
-            bfr[j][0].u = *(const uint4*)(s_ + j * 2048 + fo0);                                                                   \
-            bfr[j][1].u = *(const uint4*)(s_ + j * 2048 + fo1);                                                                   \
-        }                                                                                                                         \
-    }
-#define XL_READ_B_TO(D0, J0, NJ, buf_)                                                                                            \
-    {                                                                                                                             \
-        const unsigned char* s_ = smem + (buf_) * B_STRIDE + B_BASE + b_rd;                                                       \
+        const unsigned char* s_ = smem + (buf_) * BUF + b_rd;                                                                     \
         _Pragma("unroll") for (int j = 0; j < (NJ); ++j) {                                                                        \
             bfr[(D0) + j][0].u = *(const uint4*)(s_ + ((J0) + j) * 2048 + fo0);                                                   \
             bfr[(D0) + j][1].u = *(const uint4*)(s_ + ((J0) + j) * 2048 + fo1);                                                   \
         }                                                                                                                         \
     }
-#define XL_MMA_TO(h, D0, J0, NJ)                                                                                                  \
-    if (do_mma) {                                                                                                                 \
+    // A half h x B tiles J0 .. J0 + NJ - 1 (in registers D0 ..).  D = Wfrag x Afrag: the accumulator holds 4 consecutive n (rows of D) of one m (column of D) per lane
+#define XL_MMA(h, D0, J0, NJ)                                                                                                     \
+    {                                                                                                                             \
         __builtin_amdgcn_s_setprio(1);                                                                                            \
         _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                                          \
             _Pragma("unroll") for (int i = 0; i < TIH; ++i)                                                                       \
                 _Pragma("unroll") for (int j = 0; j < (NJ); ++j)                                                                  \
                     acc[(h) * TIH + i][(J0) + j] =                                                                                \
-                        MDX_MFMA_16x16x32(bfr[(D0) + j][kk].v, af[i][kk].v, acc[(h) * TIH + i][(J0) + j]); \
-        __builtin_amdgcn_s_setprio(0);                                                                                            \
-    }
-    // D = Wfrag x Afrag: the accumulator holds 4 consecutive n (rows of D) of one m (column of D) per lane
-#define XL_MMA(h, J0, NJ)                                                                                                         \
-    if (do_mma) {                                                                                                                 \
-        __builtin_amdgcn_s_setprio(1);                                                                                            \
-        _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                                          \
-            _Pragma("unroll") for (int i = 0; i < TIH; ++i)                                                                       \
-                _Pragma("unroll") for (int j = (J0); j < (J0) + (NJ); ++j)                                                        \
-                    acc[(h) * TIH + i][j] =                                                                                       \
-                        MDX_MFMA_16x16x32(bfr[j][kk].v, af[i][kk].v, acc[(h) * TIH + i][j]);       \
-        __builtin_amdgcn_s_setprio(0);                                                                                            \
-    }
-    // MFMA segment of the two-phase schedule: one A half x every B tile, with up to four DMA pieces interleaved between the MFMAs
-    // (pinned by sched_barrier: an LDS-DMA issued among MFMAs costs ~60 cycles of this wave's issue slot, hidden under the matrix
-    // pipe's 16 cycles per MFMA; in the load segment the same instruction costs 100-185 and sits on the critical path).
-#define XL_MSEG(h, I0, I1, I2, I3)                                                                                                \
-    {                                                                                                                             \
-        __builtin_amdgcn_s_setprio(1);                                                                                            \
-        constexpr int P_ = 2 * TIH;                                                                                               \
-        _Pragma("unroll") for (int pr = 0; pr < P_; ++pr) {                                                                       \
-            const int kk = pr / TIH, i = pr % TIH;                                                                                \
-            if (pr == 1) { I0 }                                                                                                   \
-            if (pr == 1 + (P_ - 1) / 4) { I1 }                                                                                    \
-            if (pr == 1 + 2 * (P_ - 1) / 4) { I2 }                                                                                \
-            if (pr == 1 + 3 * (P_ - 1) / 4) { I3 }                                                                                \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-            if (do_mma) {                                                                                                         \
-                _Pragma("unroll") for (int j = 0; j < TJ; ++j)                                                                    \
-                    acc[(h) * TIH + i][j] =                                                                                       \
-                        MDX_MFMA_16x16x32(bfr[j][kk].v, af[i][kk].v, acc[(h) * TIH + i][j]);       \
-            }                                                                                                                     \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-        }                                                                                                                         \
+                        MDX_MFMA_16x16x32(bfr[(D0) + j][kk].v, af[i][kk].v, acc[(h) * TIH + i][(J0) + j]);                        \
         __builtin_amdgcn_s_setprio(0);                                                                                            \
     }
     // end of a load segment: this wave's fragment reads have RETURNED before the barrier (so a unit may be refilled by anyone one
@@ -450,72 +303,6 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
         }
     }
     XL_STAMP(1)
-    if constexpr (KXS) {
-        // ===== schedule 4: the 256 x 320 quadrant order with ONE A slab per (channel block, ky) shared by its three kx slabs ==================
-        //   group g = (cb, ky) = slabs T = 3 g + kx; A buffer g & 1, B buffer T & 1; per slab the quadrants of the 320-wide schedule:
-        //   reads:   q0 A0,B0   q1 A1   q2 B1   q3 A0
-        //   issues:  q0 A0(g+1) [kx 0]   q1 B0(T+2)   q2 A1(g+1) + the halo piece [kx 1]   q3 B1(T+2)
-        //   A buffer (g+1) & 1 was last read by group g - 1; B0 / B1 of buffer T & 1 were read in q0 / q2 of this slab (as in the per-slab schedule).
-        //   wait in q3(T) for everything up to B1(T+1) (issued in q3(T-1)): the pieces issued during slab T follow it:
-        //     kx 0: PA + PB0 + PB1   kx 1: PB0 + PA + 1 + PB1   kx 2: PB0 + PB1 (the next group's A, issued in the two slabs before, is older)
-        //   last group: no A is issued, and its last two slabs issue no B either (as the per-slab schedule's tail)
-        const int ng = nt / 3;                                       // nt = 9 Cin / 64
-        int xs_ky = 0, xs_so = 0;                                    // ky / scalar offset of the group being ISSUED
-        auto xs_group = [&](int g_) { const int cb_ = g_ / 3; xs_ky = g_ - cb_ * 3; xs_so = xs_ky * p.Wi * row_bytes + cb_ * 128; };
-        xs_group(0);
-        XS_ISSUE_A0(0)
-        XS_ISSUE_A1X(0)
-        XS_ISSUE_B(0, 0)
-        XS_ISSUE_B(1, 0)
-        XS_ISSUE_B(0, 1)
-        XS_ISSUE_B(1, 1)
-        xl_wait_vmcnt<PB0 + PB1>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        XL_STAMP(2)
-        if (grp == 1) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ONE loop over the slabs (kx, the group and its A buffer are scalar state): as two nested loops the accumulators were loop-carried through
-        // both headers and the allocator copied all 160 of them every slab (78 v_mov_b64 per iteration in the .s)
-        int kx = 0, g = 0, ab = 0;
-        bool more = ng > 1;
-        xs_group(1);
-        for (int t = 0; t < nt; ++t) {
-            const int buf = t & 1;
-            // fragment offset (k32 step 0; step 1 = ^ 64) of row (lane & 15) + kx — tile row blocks are multiples of 16, they do not change
-            // row & 7 — and the border bits of this tap: left border for kx 0, right border for kx 2, none for the centre tap
-            const int r_ = (lane & 15) + kx;
-            const int xs_f0 = a_rd + r_ * 128 + (((lane >> 4) ^ (r_ & 7)) << 4);
-            const unsigned xs_bsel = kx == 0 ? (xs_bits >> 16) & 0xffu : kx == 2 ? xs_bits >> 24 : 0u;
-            XS_READ_A(0, ab)
-            XL_READ_B_TO(0, 0, TJ0, buf)
-            if (kx == 0) XS_ISSUE_A0(g + 1)
-            XL_SEG_END()
-            XL_MMA_TO(0, 0, 0, TJ0)
-            XL_MMA_END()
-            XS_READ_A(1, ab)
-            XS_ISSUE_B(0, t + 2)
-            XL_SEG_END()
-            XL_MMA_TO(1, 0, 0, TJ0)
-            XL_MMA_END()
-            XL_READ_B_TO(0, TJ0, TJ1, buf)
-            if (kx == 1) XS_ISSUE_A1X(g + 1)
-            XL_SEG_END()
-            XL_MMA_TO(1, 0, TJ0, TJ1)
-            XL_MMA_END()
-            XS_READ_A(0, ab)
-            XS_ISSUE_B(1, t + 2)
-            if (kx == 0) { if (more) xl_wait_vmcnt<PA + PB0 + PB1>(); else xl_wait_vmcnt<PB0 + PB1>(); }
-            else if (kx == 1) { if (more) xl_wait_vmcnt<PB0 + PA + 1 + PB1>(); else xl_wait_vmcnt<0>(); }
-            else { if (more) xl_wait_vmcnt<PB0 + PB1>(); else xl_wait_vmcnt<0>(); }
-            XL_SEG_END()
-            XL_MMA_TO(0, 0, TJ0, TJ1)
-            XL_MMA_END()
-            if (++kx == 3) { kx = 0; ++g; ab ^= 1; more = g + 1 < ng; xs_group(g + 1); }
-        }
-    } else
     if constexpr (BN == 320) {
         // ===== 256 x 320: quadrant order (A0,B0) (A1,B0) (A1,B1) (A0,B1) so that B0 and B1 are never live together (160 accumulators
         // leave room for one A half + 3 B tiles); A0 is read twice per slab (34 instead of 26 fragment reads: LDS port time is not the
@@ -542,83 +329,30 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
         for (int t = 0; t < nt; ++t) {
             const int buf = t & 1;
             XL_READ_A(0, buf)
-            XL_READ_B_TO(0, 0, TJ0, buf)
+            XL_READ_B(0, 0, TJ0, buf)
             XL_ISSUE_A(0, t + 1)
             XL_SEG_END()
-            XL_MMA_TO(0, 0, 0, TJ0)
+            XL_MMA(0, 0, 0, TJ0)
             XL_MMA_END()
             XL_READ_A(1, buf)
             XL_ISSUE_B(0, t + 2)
             XL_SEG_END()
-            XL_MMA_TO(1, 0, 0, TJ0)
+            XL_MMA(1, 0, 0, TJ0)
             XL_MMA_END()
-            XL_READ_B_TO(0, TJ0, TJ1, buf)
+            XL_READ_B(0, TJ0, TJ1, buf)
             XL_ISSUE_A(1, t + 2)
             XL_SEG_END()
-            XL_MMA_TO(1, 0, TJ0, TJ1)
+            XL_MMA(1, 0, TJ0, TJ1)
             XL_MMA_END()
             XL_READ_A(0, buf)
             XL_ISSUE_B(1, t + 2)
             if (t + 2 < nt) xl_wait_vmcnt<INFLIGHT>(); else xl_wait_vmcnt<0>();
             XL_SEG_END()
-            XL_MMA_TO(0, 0, TJ0, TJ1)
+            XL_MMA(0, 0, TJ0, TJ1)
             XL_MMA_END()
         }
-    } else if constexpr (SCHED == 2 || SCHED == 3) {
-        // ===== schedule 2: schedule 0's quadrants with every refill >= 2 phases after the slot's last read, so the fragment reads'
-        // lgkmcnt(0) can sit AFTER the barrier (the load segment ends when the reads are ISSUED; their latency overlaps the barrier).
-        // schedule 3: same refill order, lgkmcnt(0) before the barrier, DMA issued after it (no contention with the wave's own reads).
-        //   issue order per wave: A1(t+1)@q0  B0(t+1)@q1  A0(t+2)@q2  B1(t+2)@q3 ; reads: q0 A0,B0  q1 B1  q2 A1
-        //   wait in q3(t) for B0(t+1) (and everything older): followed by A0(t+2), B1(t+2) -> vmcnt(PA + PB1)
-        XL_ISSUE_A(0, 0)
-        XL_ISSUE_B(1, 0)
-        XL_ISSUE_A(1, 0)
-        XL_ISSUE_B(0, 0)
-        XL_ISSUE_A(0, 1)
-        XL_ISSUE_B(1, 1)
-        if (nt > 1) xl_wait_vmcnt<PA + PB1>(); else xl_wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (grp == 1) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#define XL_SEG2(ISSUE)                                                                                                            \
-        if constexpr (SCHED == 2) {                                                                                               \
-            ISSUE                                                                                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-            __builtin_amdgcn_s_barrier();                                                                                         \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-        } else {                                                                                                                  \
-            xl_wait_lgkm0();                                                                                                      \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-            ISSUE                                                                                                                 \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-            __builtin_amdgcn_s_barrier();                                                                                         \
-            __builtin_amdgcn_sched_barrier(0);                                                                                    \
-        }
-        for (int t = 0; t < nt; ++t) {
-            const int buf = t & 1;
-            XL_READ_A(0, buf)
-            XL_READ_B(0, TJ0, buf)
-            XL_SEG2(XL_ISSUE_A(1, t + 1))
-            XL_MMA(0, 0, TJ0)
-            XL_MMA_END()
-            XL_READ_B(TJ0, TJ1, buf)
-            XL_SEG2(XL_ISSUE_B(0, t + 1))
-            XL_MMA(0, TJ0, TJ1)
-            XL_MMA_END()
-            XL_READ_A(1, buf)
-            XL_SEG2(XL_ISSUE_A(0, t + 2))
-            XL_MMA(1, TJ0, TJ1)
-            XL_MMA_END()
-            XL_SEG2(XL_ISSUE_B(1, t + 2) if (t + 2 < nt) xl_wait_vmcnt<PA + PB1>(); else xl_wait_vmcnt<0>();)
-            XL_MMA(1, 0, TJ0)
-            XL_MMA_END()
-        }
-#undef XL_SEG2
-    } else     if constexpr (SCHED == 0) {
-        // ===== schedule 0: four quadrant phases per slab, one unit refilled per load segment ==========================================
+    } else {
+        // ===== 256 x 256 / 256 x 160: four quadrant phases per slab, one unit refilled per load segment ==============================
         // units A0, B0, B1, A1 (the rows the quadrants (A0,B0) (A0,B1) (A1,B1) (A1,B0) read first); a unit's slot is refilled one
         // phase after its last fragment read, for the slab two ahead; ONE counted wait per slab.
         constexpr int INFLIGHT = PA + PB0 + PB1;                     // A0, B0, B1 of the next slab follow a slab's last unit (A1)
@@ -641,71 +375,29 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
             const int buf = t & 1;
             // q0: quadrant (A0, B0).  Reads A0, B0; refills A1 of slab t + 1 (last read in q2 of slab t - 1).
             XL_READ_A(0, buf)
-            XL_READ_B(0, TJ0, buf)
+            XL_READ_B(0, 0, TJ0, buf)
             XL_ISSUE_A(1, t + 1)
             XL_SEG_END()
-            XL_MMA(0, 0, TJ0)
+            XL_MMA(0, 0, 0, TJ0)
             XL_MMA_END()
             // q1: (A0, B1).  Reads B1; refills A0 of slab t + 2 (last read in q0).
-            XL_READ_B(TJ0, TJ1, buf)
+            XL_READ_B(TJ0, TJ0, TJ1, buf)
             XL_ISSUE_A(0, t + 2)
             XL_SEG_END()
-            XL_MMA(0, TJ0, TJ1)
+            XL_MMA(0, TJ0, TJ0, TJ1)
             XL_MMA_END()
             // q2: (A1, B1).  Reads A1; refills B0 of slab t + 2 (last read in q0).
             XL_READ_A(1, buf)
             XL_ISSUE_B(0, t + 2)
             XL_SEG_END()
-            XL_MMA(1, TJ0, TJ1)
+            XL_MMA(1, TJ0, TJ0, TJ1)
             XL_MMA_END()
             // q3: (A1, B0), B0 still in registers.  Refills B1 of slab t + 2 (last read in q1); slab t + 1 must have landed: its last
             // unit (A1, issued in q0) is followed by exactly the three units A0, B0, B1 of slab t + 2 when that slab exists.
             XL_ISSUE_B(1, t + 2)
             if (t + 2 < nt) xl_wait_vmcnt<INFLIGHT>(); else xl_wait_vmcnt<0>();
             XL_SEG_END()
-            XL_MMA(1, 0, TJ0)
-            XL_MMA_END()
-        }
-    } else {
-        // ===== schedule 1: two phases per slab (A half x all B tiles), DMA issued from INSIDE the MFMA segments ======================
-        // Round-2 ablation of schedule 0 (profiles/README.md): per slab and wave group the serial path is L + M with L = 24 fragment
-        // reads (~380 cycles) + 8 DMA issues (~100 each in a load segment) + 4 exposed LDS latencies vs M = 1024 cycles of MFMA
-        // issue, i.e. ~2.6 k + 8 barriers against the matrix pipe's 2.05 k per slab.  Here L carries only the fragment reads and two
-        // latencies, the DMA instructions ride between the MFMAs (whose wave has 12 idle issue cycles per MFMA), and there are
-        // 4 barriers per slab.
-        //   P0(t): L: read A0, B(all) of slab t; wait for A1(t)          M: A0 x B, issuing B1(t+1), A1(t+1) into the other buffer
-        //   P1(t): L: read A1 of slab t; wait for A0, B0, B1 of t+1      M: A1 x B, issuing A0(t+2), B0(t+2) into this buffer
-        // Issue order per wave: ... A1(t) | A0(t+1) B0(t+1) | B1(t+1) A1(t+1) | A0(t+2) B0(t+2) ...
-        //   wait in P0(t): A1(t) is followed by A0(t+1), B0(t+1)          -> vmcnt(PA + PB0)   (0 past the end)
-        //   wait in P1(t): B1(t+1) is followed by A1(t+1)                 -> vmcnt(PA)
-        // Slot reuse: B1/A1 of the other buffer were last read in P0(t-1) / P1(t-1); A0/B0 of this buffer in P0(t) — every refill
-        // is issued at least one full barrier interval after both groups' reads of the slot returned (lgkmcnt(0) before the barrier).
-        XL_ISSUE_A(0, 0)
-        XL_ISSUE_B(0, 0)
-        XL_ISSUE_B(1, 0)
-        XL_ISSUE_A(1, 0)
-        XL_ISSUE_A(0, 1)
-        XL_ISSUE_B(0, 1)
-        if (nt > 1) xl_wait_vmcnt<PA + PB0>(); else xl_wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        XL_STAMP(2)
-        if (grp == 1) {
-            __builtin_amdgcn_s_barrier();
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        for (int t = 0; t < nt; ++t) {
-            const int buf = t & 1;
-            XL_READ_A(0, buf)
-            XL_READ_B(0, TJ, buf)
-            if (t + 1 < nt) xl_wait_vmcnt<PA + PB0>(); else xl_wait_vmcnt<0>();
-            XL_SEG_END()
-            XL_MSEG(0, XL_PIECE_B(1, 0, t + 1), XL_PIECE_B(1, 1, t + 1), XL_PIECE_A(1, 0, t + 1), XL_PIECE_A(1, 1, t + 1))
-            XL_MMA_END()
-            XL_READ_A(1, buf)
-            if (t + 1 < nt) xl_wait_vmcnt<PA>();
-            XL_SEG_END()
-            XL_MSEG(1, XL_PIECE_A(0, 0, t + 2), XL_PIECE_A(0, 1, t + 2), XL_PIECE_B(0, 0, t + 2), XL_PIECE_B(0, 1, t + 2))
+            XL_MMA(1, 0, 0, TJ0)
             XL_MMA_END()
         }
     }
@@ -714,28 +406,16 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
         __builtin_amdgcn_sched_barrier(0);
     }
 #undef XL_PIECE_A
-#undef XS_PIECE_A
-#undef XS_PIECE_B
-#undef XS_ISSUE_B
-#undef XS_ISSUE_A0
-#undef XS_ISSUE_A1X
-#undef XS_READ_A
 #undef XL_PIECE_B
 #undef XL_ISSUE_A
 #undef XL_ISSUE_B
 #undef XL_READ_A
 #undef XL_READ_B
-#undef XL_READ_B_TO
-#undef XL_MMA_TO
 #undef XL_MMA
-#undef XL_MSEG
 #undef XL_SEG_END
 #undef XL_MMA_END
 
     XL_STAMP(3)
-#ifdef MDX_XL_ABLATE
-    if (p.dbg & 4) return;                                       // ablation: prologue + main loop only (no epilogue at all)
-#endif
     // ---- epilogue ----
     constexpr int NH = (BN == 320) ? 2 : 1;                       // the 320-wide bf16 tile goes through LDS in two 128-row halves
     constexpr int HROWS = BM / NH;
@@ -781,11 +461,7 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
     constexpr int RIT = (HROWS + RPP - 1) / RPP;                  // passes: 16 (256-wide), 11 (320-wide half, 160-wide)
     const int rrow0 = tid / CPR, rc8 = (tid - rrow0 * CPR) * 8;
     const bool ractive = tid < RPP * CPR && n0 + rc8 < p.N;
-#ifdef MDX_XL_R2_RESIDUAL                                       // A/B side build: the 320-wide tile keeps round 2's batches of four
-    const bool rpref = NH == 1 && Rg != nullptr && p.wide && !geglu;
-#else
     const bool rpref = Rg != nullptr && p.wide && !geglu;
-#endif
     // element offset in C of row `rt` of this tile.  UP: row -> (image, low-res pixel of the phase's grid) -> the strided pixel of Y it owns
     const float up_rhw = UP ? 1.0f / (float)hw : 0.f, up_rw = UP ? 1.0f / (float)Wo : 0.f;
     auto c_off = [&](int rt) -> long {
@@ -895,9 +571,6 @@ __global__ __launch_bounds__(512, 2) void gemm_xl_kernel(GCParams p) {
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         XL_STAMP(4)
-#ifdef MDX_XL_ABLATE
-        if (p.dbg & 8) continue;                                 // ablation: accumulators staged, nothing stored
-#endif
         const int mh = m0 + hh * HROWS;
         if (p.col_split) {
             // batch-flattened output: a tile's columns are tokens of consecutive images; column n -> image n / cs, token n % cs.
@@ -1385,18 +1058,15 @@ constexpr size_t xl_smem_bytes() {
 bool xd_supported(const GCParams& q);                                          // gemm_xd.hip
 int launch_gemm_xd(const GCParams& q, int cus, hipStream_t st);
 
-template <int BN, bool CONV, int SCHED, int TAPS = 9>
+template <int BN, bool CONV, int TAPS = 9>
 static int launch_xl(const GCParams& p, hipStream_t st) {
-    constexpr size_t smem_kxs = (size_t)2 * 272 * 128 + (size_t)2 * Geo<BN>::BNP * 128;      // SCHED 4: two 272-row A buffers + two weight slabs
-    constexpr size_t smem = (SCHED == 4 && smem_kxs > xl_smem_bytes<BN>()) ? smem_kxs : xl_smem_bytes<BN>();
+    constexpr size_t smem = xl_smem_bytes<BN>();
     static_assert(smem <= 163840, "LDS budget");
-    auto kern = gemm_xl_kernel<BN, CONV, SCHED, TAPS>;
+    auto kern = gemm_xl_kernel<BN, CONV, TAPS>;
     if (int rc = ensure_dyn_smem((const void*)kern, smem, "xl")) return rc;
     GCParams q = p;
     q.mt = TAPS == 4 ? up_mtiles(p) : (p.M + 255) / 256; q.nt = (p.N + BN - 1) / BN;
     const int swz = (int)opt(OPT_GEMM_SWZ);
-    const int dbg = (int)opt(OPT_XL_DBG);
-    q.dbg = dbg;
     q.swz = swz && q.nt > 1 && q.mt >= 64;
     unsigned nblk_raster = 0;
     const int raster = (int)opt(OPT_XL_RASTER);
@@ -1415,7 +1085,7 @@ static int launch_xl(const GCParams& p, hipStream_t st) {
     q.timing = (timing && p.ws && (long)nblk_t * 64 <= p.ws_bytes) ? (unsigned long long*)p.ws : nullptr;
     const unsigned nblk = nblk_t;
     q.nblk = (int)nblk;
-    if constexpr (BN == 256 && !CONV && SCHED == 0) {
+    if constexpr (BN == 256 && !CONV) {
         // persistent form (gemm_xlp_kernel): one workgroup per CU walks the tile order, the next tile's first slabs land while this one
         // is stored.  Plain / GEGLU epilogue, optional residual, 16-byte C rows, enough tiles for the walk to matter.
         static const int cus = [] { int d = 0, n = 256; if (hipGetDevice(&d) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d); return n > 0 ? n : 256; }();
@@ -1442,39 +1112,24 @@ static int launch_xl(const GCParams& p, hipStream_t st) {
     }
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), smem, st, q);
     char tag[96];
-    mdx_route::tag_xl(tag, sizeof tag, BN, CONV, SCHED == 4, TAPS == 4);
+    mdx_route::tag_xl(tag, sizeof tag, BN, CONV, TAPS == 4);
     return check_launch(tag);
 }
 
 // Can the XL main loop run this problem at all?  (gemm_route.h: the conditions, and the cost model that decides whether it should.)
 bool xl_supported(const GCParams& p, bool conv, int bn) { return mdx_route::xl_supported(route_in(p, conv), bn); }
 
-// MDX_XL_SCHED: 0 (default) = four quadrant phases per slab, refill in the load segments; 1 = two phases per slab with the DMA
-// issued between the MFMAs (measured 10 % slower: the DMA issue lengthens the MFMA segments, which are the serial resource);
-// 2 / 3 = quadrant variants (see the kernel).
 int launch_gemm_xl(const GCParams& p, bool conv, int bn, hipStream_t st) {
     if (p.rowstat) return set_error(MDX_EINVAL, "gemm_xl: rowstat_out reached a route that does not emit row statistics");
-    const int sched = (int)opt(OPT_XL_SCHED);
     if (p.up2) {
         if (!conv || !xl_supported(p, true, bn)) return set_error(MDX_EINVAL, "gemm_xl: upsampled-2x conv on an unsupported shape");
-        return bn == 320 ? launch_xl<320, true, 0, 4>(p, st) : launch_xl<256, true, 0, 4>(p, st);
+        return bn == 320 ? launch_xl<320, true, 4>(p, st) : launch_xl<256, true, 4>(p, st);
     }
-#define XL_GO(BN_, S_) (conv ? launch_xl<BN_, true, S_>(p, st) : launch_xl<BN_, false, S_>(p, st))
-    if (bn == 320) {
-        // 3x3 / stride 1 convs: the three horizontal taps of a (channel block, ky) share one A slab (schedule 4; XL_KXSHARE = 0: per-tap slabs, A/B)
-        // Built, correct (tests/test_routes_gpu.py::test_xl_conv in a -DMDX_XL_KXS build) and 18-21 % SLOWER than one slab per tap: the border
-        // selects + per-piece offset arithmetic put ~100 more VALU instructions per slab into the load segments, which are the serial resource
-        // (profiles/r06_xl_kxshare_ab.log) — more than the -29 % operand bytes buy (+6...8 %, profiles/r06_xl_a_bytes_ablation.log).  Not in the
-        // product build; `make side SIDE=kxs FLAGS=-DMDX_XL_KXS` builds it for A/B runs.
-#ifdef MDX_XL_KXS
-        if (conv && opt(OPT_XL_KXSHARE) && p.sh == 1 && p.sw == 1 && p.Hi == p.Ho && p.Wi == p.Wo && p.Wo >= 2 && (p.K / 64) % 9 == 0 && p.N % 320 == 0)
-            return launch_xl<320, true, 4>(p, st);
-#endif
-        return XL_GO(320, 0);
+    switch (bn) {
+        case 320: return conv ? launch_xl<320, true>(p, st) : launch_xl<320, false>(p, st);
+        case 256: return conv ? launch_xl<256, true>(p, st) : launch_xl<256, false>(p, st);
+        default: return conv ? launch_xl<160, true>(p, st) : launch_xl<160, false>(p, st);
     }
-    if (bn == 256) return sched == 1 ? XL_GO(256, 1) : sched == 2 ? XL_GO(256, 2) : sched == 3 ? XL_GO(256, 3) : XL_GO(256, 0);
-    return sched == 1 ? XL_GO(160, 1) : sched == 2 ? XL_GO(160, 2) : sched == 3 ? XL_GO(160, 3) : XL_GO(160, 0);
-#undef XL_GO
 }
 
 }  // namespace mdx

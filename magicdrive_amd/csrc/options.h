@@ -46,10 +46,7 @@ namespace mdx {
     X(GEMM_FLATTEN, 1, "batched shared-A GEMM as ONE col_split XL launch") \
     X(CONV_CIMAJOR, 1, "channel-block-major K order of implicit-GEMM convs") \
     X(WS_SLOTS, 512, "workgroup slots the gemm_ws M walkers are sized for") \
-    X(WS_DBG, 0, "gemm_ws ablation bits (wrong results)") \
-    X(XL_DBG, 0, "ablation bits, only in -DMDX_XL_ABLATE builds") \
     X(XL_TIMING, 0, "per-workgroup s_memtime stamps into the op workspace") \
-    X(XL_SCHED, 0, "XL main-loop schedule variant 0..3 (0 = four quadrant phases)") \
     X(GN_REVERSE, 1, "two-stage GroupNorm: statistics pass reads the tensor back to front (Infinity-Cache reuse between producer / passes)") \
     X(GN_FINALIZE_CHUNKS, 16, "two-stage GroupNorm: with more chunks per image than this the chunk partials are combined once by gn_finalize_kernel (0 = always in the apply pass)") \
     X(GN_ONE_KERNEL_ELEMS, (4L << 20), "GroupNorm tensors of at most this many elements (all images) take the one-launch kernel (one workgroup per (image, group)) instead of the two streaming passes") \
@@ -57,7 +54,6 @@ namespace mdx {
     X(XL_PERSIST, 1, "256x256 XL GEMMs (plain / GEGLU, optional residual) on the persistent kernel gemm_xlp_kernel") \
     X(XD, 0, "W-direct persistent GEMM (gemm_xd.hip: weights global -> registers, finished tile stored under the next tile's main loop) for the 256x256 XL GEMMs whose descriptor carries Wq (K % 128 == 0, K >= 640); bit-identical to gemm_xlp_kernel, measured 0.89-1.04x of it (profiles/r06_xd_ab.log): off by default") \
     X(XL_RASTER, 2, "XL tile order: 0 row-major, 1 XCD-strided M-tiles, 2 XCD-blocked (M-group x N-group panels per XCD)") \
-    X(XL_KXSHARE, 1, "only in -DMDX_XL_KXS side builds: 320-wide XL 3x3 / stride 1 convs share one A slab in LDS between the three horizontal taps of a (channel block, ky) (schedule 4; measured slower, gemm_xl.hip: launch_gemm_xl)") \
     X(XL_GM, 0, "XL_RASTER 2: force the M-tiles per panel (0 = cost model, xl_layout.h: raster_shape)") \
     X(XL_GN, 0, "XL_RASTER 2: force the N-tiles per panel (0 = cost model)") \
     X(STREAMS, 2, "host side (pipeline): HIP streams a pipe() call spreads its scene chunks over (chunks of >= 16 scenes, one plan + hipGraph each)") \

@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """Time the level-0 LayerNorm -> projection pairs with the norm inside the weight-stationary GEMM (MdxGemmDesc.ln_eps) against the same
 projection on pre-normalised rows and against LayerNorm + projection — the A/B tool for gemm_ws.hip's fused-LayerNorm variants
-(side builds with -DMDX_WS_LN_ABLATE=1|2|3 through MDX_LIB_PATH separate the sums, the extra fragment read and the epilogue).
 Usage: python tools/lnone.py [--views 768] [--reps 5]"""
 import argparse
 import os

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Time a few representative shapes of the XL GEMM / conv main loop (gemm_xl.hip) — the A/B tool for its schedule knobs.
-Usage: [MDX_XL_DBG=..] python tools/xlone.py [--views 384] [--reps 10] [--only c160,c256,...]"""
+Usage: python tools/xlone.py [--views 384] [--reps 10] [--only c160,c256,...]"""
 import argparse
 import os
 import sys
