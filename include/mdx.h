@@ -42,7 +42,7 @@ extern "C" {
 #define MDX_ELAUNCH (-2)     /* hip launch / runtime error */
 #define MDX_EUNSUPPORTED (-3)
 
-#define MDX_ABI_VERSION 11
+#define MDX_ABI_VERSION 12
 
 /* ---- epilogue flags shared by GEMM / conv ------------------------------- */
 #define MDX_EPI_NONE 0
@@ -216,6 +216,15 @@ int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream);
  *   - ldo % 4 == 0, sO % 4 == 0 and O must be 8-byte aligned (an O row is written as 8-byte pieces — ldo % 8 == 4 is served).
  *   - B, H, Tq, Tk fit a 32-bit int; joint must be 0 or 1; nsrc must be 1..2 (joint: 1..8); nsrc > 1 needs a kvmap (4-byte aligned);
  *     q_prescaled must be 0 or 1.
+ * Short sequences, V row-major, causal mask (ABI 12; CLIP's text encoder, transformers/models/clip/modeling_clip.py: CLIPAttention with the
+ * causal mask of CLIPTextTransformer — 77 tokens, 12 heads of 64).  With causal == 0 and v_rowmajor == 0 everything above holds unchanged.
+ *   v_rowmajor == 1: the third operand is V itself, [Bkv][Tk][H*d] — element (b,t,h,j) at Vt + b*sV + t*ldv + h*d + j, ldv a token stride —
+ *     so Q, K and V can be the three column blocks of one fused [M][3C] projection buffer.  One kernel serves it (csrc/attention_short.hip:
+ *     one workgroup per (batch, head), the head's whole K and V in LDS, one softmax pass, V transposed by the LDS read):
+ *       - SERVED: Tq <= 128, Tk <= 128 and d in {32, 64};  any other d, or a larger Tq / Tk, returns MDX_EUNSUPPORTED.
+ *       - nsrc must be 1, joint 0, q_prescaled 0 (MDX_EINVAL, the message names the field); kvmap is ignored.
+ *       - ldq, ldk, ldv, sQ, sK, sV multiples of 8, ldv >= H*d, Q, K, Vt 16-byte aligned; O as above.
+ *   causal == 1: query t sees keys 0..t.  Needs v_rowmajor == 1 and Tq == Tk (MDX_EINVAL otherwise); causal must be 0 or 1.
  */
 typedef struct MdxAttnDesc {
     const void* Q; const void* K; const void* Vt; void* O;
@@ -227,6 +236,8 @@ typedef struct MdxAttnDesc {
     int64_t q_prescaled;   /* 1: Q already carries scale * log2(e) (folded into the to_q weights when they were packed): `scale` is ignored,
                             * Q K^T is used as the base-2 exponent directly — lets the head-dim-40 kernel subtract the running maximum
                             * inside the QK MFMA (attention2.hip: FOLD).  0: plain Q, softmax(scale * Q K^T) as in the reference. */
+    int64_t causal;        /* ABI 12.  1: query t attends to keys 0..t only (needs v_rowmajor == 1 and Tq == Tk).  0: every key. */
+    int64_t v_rowmajor;    /* ABI 12.  1: `Vt` holds V row-major [Bkv][Tk][H*d] with token stride ldv (short-sequence kernel).  0: V^T as above. */
 } MdxAttnDesc;
 int mdx_attention_bf16(const MdxAttnDesc* d, void* stream);
 
@@ -312,11 +323,16 @@ int mdx_fourier_embed(const MdxFourierDesc* d, void* stream);
 /*
  * mdx_gather_rows — Y[i,:] = m[i] ? T[idx[i],:] : null[:]  (class-token lookup with null blend,
  * bbox_embedder.py:179-180; idx may be -1 where mask is 0).
- * Requirements (MDX_EINVAL): C and n_rows fit a 32-bit int, n_rows must be positive; idx 8-byte aligned, T / Y / null_row 2-byte aligned.
+ * Optional added row (ABI 12; the fields were reserved_p / reserved0): add != NULL gives
+ *     Y[i,:] = (m[i] ? T[idx[i],:] : null[:]) + add[i % add_period, :]
+ * with add a 16-bit [add_period][ldt] table, the sum taken in fp32 and rounded once — token + position embedding of a text encoder
+ * (transformers/models/clip/modeling_clip.py: CLIPTextEmbeddings) in one launch.  add == NULL: the plain gather, unchanged.
+ * Requirements (MDX_EINVAL): C and n_rows fit a 32-bit int, n_rows must be positive; idx 8-byte aligned, T / Y / null_row 2-byte aligned;
+ * with add: add 2-byte aligned, add_period positive.
  */
 typedef struct MdxGatherDesc {
-    const void* T; void* Y; const int64_t* idx; const uint8_t* mask; const void* null_row; void* reserved_p;
-    int64_t n, C, ldt, ldy, n_rows, reserved0;
+    const void* T; void* Y; const int64_t* idx; const uint8_t* mask; const void* null_row; const void* add;
+    int64_t n, C, ldt, ldy, n_rows, add_period;
 } MdxGatherDesc;
 int mdx_gather_rows(const MdxGatherDesc* d, void* stream);
 

@@ -369,6 +369,25 @@ __global__ __launch_bounds__(256) void gather_kernel(GatherParams p) {
     p.Y[i * p.ldy + c] = v;
 }
 
+// gather + added row (MdxGatherDesc.add: token + position embedding): fp32 sum of the two 16-bit values, rounded once
+__global__ __launch_bounds__(256) void gather_add_kernel(GatherParams p, const bf16_t* add, long add_period) {
+    long id = (long)blockIdx.x * 256 + threadIdx.x;
+    if (id >= p.n * p.C) return;
+    long i = id / p.C;
+    int c = (int)(id - i * p.C);
+    bool m = p.mask ? p.mask[i] != 0 : true;
+    bf16_t v;
+    if (m) {
+        long r = p.idx[i];
+        if (r < 0) r += p.n_rows;
+        if (r < 0 || r >= p.n_rows) r = 0;
+        v = p.T[r * p.ldt + c];
+    } else {
+        v = p.null_row ? p.null_row[c] : (bf16_t)0;
+    }
+    p.Y[i * p.ldy + c] = f2bf(bf2f(v) + bf2f(add[(i % add_period) * p.ldt + c]));
+}
+
 struct TimeEmbParams { const float* t; void* Y; long n; int dim, flip; long ldy; float shift, max_period; int y_f32; };
 
 __global__ __launch_bounds__(256) void timeemb_kernel(TimeEmbParams p) {
@@ -594,6 +613,13 @@ extern "C" int mdx_gather_rows(const MdxGatherDesc* d, void* stream) {
     if (d->n_rows <= 0 && d->n > 0 && d->C > 0) return set_error(MDX_EINVAL, "mdx_gather_rows: n_rows must be positive");
     GatherParams p{(const bf16_t*)d->T, (bf16_t*)d->Y, d->idx, d->mask, (const bf16_t*)d->null_row, d->n, (int)d->C, d->ldt, d->ldy, (int)d->n_rows};
     long total = p.n * p.C;
+    if (d->add) {
+        if ((uintptr_t)d->add & 1) return set_error(MDX_EINVAL, "mdx_gather_rows: add must be 2-byte aligned");
+        if (d->add_period <= 0) return set_error(MDX_EINVAL, "mdx_gather_rows: add_period=%ld must be positive", (long)d->add_period);
+        if (total <= 0) return MDX_OK;
+        hipLaunchKernelGGL(gather_add_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, (const bf16_t*)d->add, (long)d->add_period);
+        return check_launch("gather_add_kernel");
+    }
     if (total <= 0) return MDX_OK;
     hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("gather_kernel");

@@ -26,7 +26,8 @@ _lib = None
 class MdxAttnDesc(ctypes.Structure):               # mirrors include/mdx.h MdxAttnDesc field for field
     _fields_ = [(n, ctypes.c_void_p) for n in "Q K Vt O kvmap reserved_p".split()] + \
                [(n, ctypes.c_int64) for n in "B H Tq Tk d nsrc ldq sQ ldk sK ldv sV ldo sO".split()] + \
-               [("scale", ctypes.c_double), ("joint", ctypes.c_int64), ("q_prescaled", ctypes.c_int64)]   # q_prescaled = 0: plain Q
+               [("scale", ctypes.c_double), ("joint", ctypes.c_int64), ("q_prescaled", ctypes.c_int64),   # q_prescaled = 0: plain Q
+                ("causal", ctypes.c_int64), ("v_rowmajor", ctypes.c_int64)]                                  # ABI 12; 0 / 0: no mask, V^T operand
 
 
 def _mdx():
@@ -46,7 +47,8 @@ class MdxAttnProcessor:
 
     def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
         if attention_mask is not None:
-            raise NotImplementedError("MagicDrive's sampler never passes an attention mask (blocks.py:144-238)")
+            raise NotImplementedError("MagicDrive's sampler never passes an attention mask (blocks.py:144-238); the library's only mask is "
+                                      "MdxAttnDesc.causal, for short sequences with a row-major V (the text encoder)")
         if not hidden_states.is_cuda:
             raise RuntimeError("MdxAttnProcessor runs on the GPU kernel; there is no CPU path")
         ctx = hidden_states if encoder_hidden_states is None else encoder_hidden_states

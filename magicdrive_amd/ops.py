@@ -256,7 +256,8 @@ class Conv:
 
 @dataclass
 class Attn:
-    """O = sum_s softmax(Q K_s^T * scale) V_s.  Q [B,Tq,C]; K [Bkv,Tk,C]; Vt [Bkv,C,ldv] (V transposed); O [B,Tq,C]."""
+    """O = sum_s softmax(Q K_s^T * scale) V_s.  Q [B,Tq,C]; K [Bkv,Tk,C]; Vt [Bkv,C,ldv] (V transposed); O [B,Tq,C].
+    v_rowmajor: Vt is V itself, [B,Tk,C] (short sequences only: MdxAttnDesc.v_rowmajor); causal: query t sees keys 0..t."""
     Q: torch.Tensor
     K: torch.Tensor
     Vt: torch.Tensor
@@ -269,14 +270,21 @@ class Attn:
     name: str = ""
     joint: bool = False                      # one softmax over the concatenated sources (neighboring_attn_type concat / self) instead of a sum of per-source attentions
     q_prescaled: bool = False                # Q already carries scale * log2(e) (folded into to_q at pack time): probabilities are exp2(Q K^T - max)
+    causal: bool = False
+    v_rowmajor: bool = False
     opcode = L.OP_ATTN
 
     def lower(self):
         Q, K, Vt, O = self.Q, self.K, self.Vt, self.O
         B, Tq, Cc = Q.shape
         _chk(Q.stride(2) == 1 and K.stride(2) == 1 and O.stride(2) == 1 and Vt.stride(2) == 1, f"attn {self.name}: inner strides")
-        _chk(Cc % self.heads == 0 and K.shape[2] == Cc and Vt.shape[1] == Cc and O.shape == Q.shape, f"attn {self.name}: shapes")
-        _chk(K.shape[1] == self.Tk and Vt.shape[2] >= self.Tk and Vt.shape[0] == K.shape[0], f"attn {self.name}: kv shapes")
+        if self.v_rowmajor:
+            _chk(Cc % self.heads == 0 and K.shape[2] == Cc and Vt.shape[2] == Cc and O.shape == Q.shape, f"attn {self.name}: shapes")
+            _chk(K.shape[1] == self.Tk and Vt.shape[1] == self.Tk and Vt.shape[0] == K.shape[0], f"attn {self.name}: kv shapes")
+        else:
+            _chk(not self.causal, f"attn {self.name}: causal needs v_rowmajor")
+            _chk(Cc % self.heads == 0 and K.shape[2] == Cc and Vt.shape[1] == Cc and O.shape == Q.shape, f"attn {self.name}: shapes")
+            _chk(K.shape[1] == self.Tk and Vt.shape[2] >= self.Tk and Vt.shape[0] == K.shape[0], f"attn {self.name}: kv shapes")
         d = L.MdxAttnDesc()
         d.Q, d.K, d.Vt, d.O = _p(Q), _p(K), _p(Vt), _p(O)
         if self.kvmap is not None:
@@ -292,6 +300,7 @@ class Attn:
         d.scale = float(self.scale)
         d.joint = int(self.joint)
         d.q_prescaled = int(self.q_prescaled)
+        d.causal, d.v_rowmajor = int(self.causal), int(self.v_rowmajor)
         _chk(self.nsrc >= 1 and (self.nsrc <= 8 if self.joint else self.nsrc <= 2), f"attn {self.name}: nsrc={self.nsrc} (joint={self.joint})")
         return self.opcode, d
 
@@ -467,6 +476,7 @@ class Gather:
     mask: Optional[torch.Tensor] = None  # uint8 [n]
     null_row: Optional[torch.Tensor] = None  # bf16 [C]
     name: str = ""
+    add: Optional[torch.Tensor] = None       # bf16 [period, C], same row stride as T: Y[i] += add[i % period] (fp32 sum, one rounding)
     opcode = L.OP_GATHER
 
     def lower(self):
@@ -476,6 +486,10 @@ class Gather:
         d = L.MdxGatherDesc()
         d.T, d.Y, d.idx, d.mask, d.null_row = _p(self.T), _p(self.Y), _p(self.idx), _p(self.mask), _p(self.null_row)
         d.n, d.C, d.ldt, d.ldy, d.n_rows = n, Cc, ldt, ldy, rows
+        if self.add is not None:
+            period, C3, lda = _rows2d(self.add)
+            _chk(C3 == Cc and lda == ldt and period > 0 and self.add.dtype == self.T.dtype, "gather: add must be [period, C] with T's row stride and dtype")
+            d.add, d.add_period = _p(self.add), period
         return self.opcode, d
 
 

@@ -76,10 +76,13 @@ class StableDiffusionBEVControlNetPipeline:
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, controlnet=None, unet=None, safety_checker=None,
-                        feature_extractor=None, torch_dtype=torch.bfloat16, vae=None, text_encoder=None, tokenizer=None, **kw):
+                        feature_extractor=None, torch_dtype=torch.bfloat16, vae=None, text_encoder=None, tokenizer=None,
+                        hip_text_encoder: bool = False, **kw):
         """`pipe_cls.from_pretrained(<sd15 dir>, controlnet=, unet=, safety_checker=None, feature_extractor=None, torch_dtype=)` —
         the call `build_pipe` makes (magicdrive/misc/test_utils.py:118-126).  Reads the SD-1.5 directory layout: `scheduler/
-        scheduler_config.json`, `vae/` (decoded on the HIP kernels), `text_encoder/` + `tokenizer/` (transformers; optional)."""
+        scheduler_config.json`, `vae/` (decoded on the HIP kernels), `text_encoder/` + `tokenizer/` (transformers; optional).  hip_text_encoder=True loads
+        `text_encoder/` with magicdrive_amd.networks.clip_text.CLIPTextModel (the library's kernels, no transformers import) instead; an
+        instance of that class can also be passed as text_encoder=."""
         root = pretrained_model_name_or_path
         sch = DDIMScheduler()
         p = os.path.join(root, "scheduler", "scheduler_config.json")
@@ -89,6 +92,9 @@ class StableDiffusionBEVControlNetPipeline:
         if vae is None and os.path.exists(os.path.join(root, "vae", "config.json")):
             from ..networks.autoencoder_kl import AutoencoderKL
             vae = AutoencoderKL.from_pretrained(os.path.join(root, "vae"), torch_dtype=torch_dtype)
+        if text_encoder is None and hip_text_encoder:
+            from ..networks.clip_text import CLIPTextModel
+            text_encoder = CLIPTextModel.from_pretrained(os.path.join(root, "text_encoder"), torch_dtype=torch_dtype or torch.bfloat16)
         if text_encoder is None and os.path.isdir(os.path.join(root, "text_encoder")):
             import transformers
             text_encoder = transformers.CLIPTextModel.from_pretrained(os.path.join(root, "text_encoder")).eval()

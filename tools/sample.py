@@ -140,7 +140,7 @@ def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, gen
         yield ti, pipe(conditional_latents=conditional_latents, generator=generator, **kw).images
 
 
-def build_pipe(ckpt: str, sd15: str, scheduler: str, device, given_view: bool = False):
+def build_pipe(ckpt: str, sd15: str, scheduler: str, device, given_view: bool = False, hip_text_encoder: bool = False):
     """The reference's build_pipe sequence (magicdrive/misc/test_utils.py:94-138) with the magicdrive_amd config strings."""
     from magicdrive_amd import schedulers
     from magicdrive_amd.misc.common import load_module
@@ -152,7 +152,8 @@ def build_pipe(ckpt: str, sd15: str, scheduler: str, device, given_view: bool = 
     ckpt = ckpt[:-1] if ckpt.endswith("/") else ckpt
     controlnet = model_cls.from_pretrained(os.path.join(ckpt, "controlnet"), torch_dtype=torch.float16).eval()
     unet = unet_cls.from_pretrained(os.path.join(ckpt, "unet"), torch_dtype=torch.float16).eval()
-    pipe = pipe_cls.from_pretrained(sd15, controlnet=controlnet, unet=unet, safety_checker=None, feature_extractor=None, torch_dtype=torch.float16)
+    pipe = pipe_cls.from_pretrained(sd15, controlnet=controlnet, unet=unet, safety_checker=None, feature_extractor=None, torch_dtype=torch.float16,
+                                    hip_text_encoder=hip_text_encoder)
     if scheduler == "unipc":
         pipe.scheduler = schedulers.UniPCMultistepScheduler.from_config(pipe.scheduler.config)
     pipe.enable_xformers_memory_efficient_attention()
@@ -244,6 +245,7 @@ def main(argv=None):
     ap.add_argument("--scheduler", choices=["unipc", "ddim"], default="unipc")
     ap.add_argument("--batch-size", type=int, default=1)
     ap.add_argument("--prompt-embeds", action="store_true", help="no text encoder available: sample with zero prompt embeddings")
+    ap.add_argument("--hip-text-encoder", action="store_true", help="encode the prompts on the HIP kernels (magicdrive_amd.networks.clip_text) instead of transformers' CLIPTextModel")
     ap.add_argument("--device", default=None, help="default: cuda:<LOCAL_RANK>")
     ap.add_argument("--gather-images", action="store_true", help="multi-rank: rank 0 writes every file from gathered uint8 images (the reference's multi-node branch); "
                                                                  "default: each rank writes its own scenes, labels are gathered (its single-node branch)")
@@ -264,7 +266,7 @@ def main(argv=None):
         mod, fn = a.pipe_factory.split(":")
         pipe = getattr(importlib.import_module(mod), fn)(a.ckpt, a.sd15, a.scheduler, device, a.cond_on_view)
     else:
-        pipe = build_pipe(a.ckpt, a.sd15, a.scheduler, device, given_view=a.cond_on_view)
+        pipe = build_pipe(a.ckpt, a.sd15, a.scheduler, device, given_view=a.cond_on_view, hip_text_encoder=a.hip_text_encoder)
     data = FolderSet(a.data)
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
