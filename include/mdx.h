@@ -225,10 +225,24 @@ int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream);
  *       - nsrc must be 1, joint 0, q_prescaled 0 (MDX_EINVAL, the message names the field); kvmap is ignored.
  *       - ldq, ldk, ldv, sQ, sK, sV multiples of 8, ldv >= H*d, Q, K, Vt 16-byte aligned; O as above.
  *   causal == 1: query t sees keys 0..t.  Needs v_rowmajor == 1 and Tq == Tk (MDX_EINVAL otherwise); causal must be 0 or 1.
+ * Key count from device memory (tk_dev, the former reserved_p; the struct's size and layout are unchanged and NULL is the old contract, so the
+ * ABI version stays 12).  For the text + camera + box context of a sampler plan built at a box capacity (the reference pads the boxes of every
+ * batch to that batch's maximum, pipeline_bev_controlnet.py:330-343, so the context length differs from call to call).  With tk_dev == NULL
+ * everything above holds unchanged, bit for bit.
+ *   tk_dev != NULL: a device pointer to ONE int32, 4-byte aligned.  Tk is then the CAPACITY: K is valid for Tk rows, V^T for Tk columns
+ *     (ldv >= Tk as above).  The kernel reads n = *tk_dev on the device when it RUNS - a replayed hipGraph sees the value current at
+ *     replay - and queries attend to keys 0 .. n-1 only; what keys n .. Tk-1 and the V^T pad columns hold never reaches O (NaN included).
+ *     The work done depends on n, not on Tk: the same n at two capacities gives bit-identical O.
+ *       - n < 1 or n > Tk cannot be reported without a sync: n is clamped to [1, Tk] for addressing and EVERY O row is written as NaN.
+ *       - SERVED (csrc/attention_ctx.hip): nsrc == 1, joint == 0, causal == 0, v_rowmajor == 0 - anything else returns MDX_EINVAL, the
+ *         message names the field; kvmap is ignored.  q_prescaled may be 0 or 1; with 0, scale must be > 0 (MDX_EINVAL).
+ *       - d in {16, 32, 40, 80, 160};  any other d returns MDX_EUNSUPPORTED.
+ *       - alignment / strides: as for the V^T form above (ldq, ldk, ldv, sQ, sK, sV multiples of 8; Q, K, Vt 16-byte, O 8-byte aligned;
+ *         ldo, sO multiples of 4); B * H * ceil(Tq / 128) must fit a 32-bit int.
  */
 typedef struct MdxAttnDesc {
     const void* Q; const void* K; const void* Vt; void* O;
-    const int32_t* kvmap; void* reserved_p;
+    const int32_t* kvmap; const int32_t* tk_dev;   /* tk_dev: NULL, or the device address of the live key count (see above; was reserved_p) */
     int64_t B, H, Tq, Tk, d, nsrc;
     int64_t ldq, sQ, ldk, sK, ldv, sV, ldo, sO;
     double scale;

@@ -3,7 +3,8 @@
 // Replaces the attention of transformers' CLIPTextModel (models/clip/modeling_clip.py: CLIPAttention under CLIPTextTransformer's causal mask;
 // the reference pipeline's `text_encoder`, magicdrive/pipeline/pipeline_bev_controlnet.py:148-165): 77 tokens, 12 heads of 64, Q / K / V the
 // three column blocks of one fused [M][3C] projection.  Also the public mdx_attention_* entry point: descriptors with causal == 0 and
-// v_rowmajor == 0 go on, untouched, to the flash kernels' entry in attention.hip (compiled as mdx_attention_long_*, launch.h).
+// v_rowmajor == 0 go on, untouched, to the flash kernels' entry in attention.hip (compiled as mdx_attention_long_*, launch.h); a descriptor
+// with tk_dev != NULL (key count read from device memory) goes, before either test, to attention_ctx.hip.
 //
 // Shape regime: Tq, Tk <= 128, d in {32, 64}.  Nothing is a multiple of the tile (T = 77), so everything is masked.
 //
@@ -41,6 +42,12 @@
 #error "attention_short.hip defines the public mdx_attention_* entry points: -DMDX_ATTN_LONG_ENTRY belongs on attention.hip only"
 #endif
 extern "C" int MDX_ATTN_LONG(const MdxAttnDesc* a, void* stream);      // attention.hip
+#if MDX_F16
+#define MDX_ATTN_CTX mdx_attention_ctx_f16
+#else
+#define MDX_ATTN_CTX mdx_attention_ctx_bf16
+#endif
+extern "C" int MDX_ATTN_CTX(const MdxAttnDesc* a, void* stream);       // attention_ctx.hip: key count read from device memory (tk_dev != NULL)
 
 namespace mdx {
 
@@ -214,6 +221,7 @@ static int launch_attn_short(const AttnShortParams& p, long blocks, bool causal,
 using namespace mdx;
 
 extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
+    if (a && a->tk_dev) return MDX_ATTN_CTX(a, stream);
     if (!a || (a->causal == 0 && a->v_rowmajor == 0)) return MDX_ATTN_LONG(a, stream);
     const char* op = MDX_F16 ? "mdx_attention_f16" : "mdx_attention_bf16";
     if (a->causal != 0 && a->causal != 1) return set_error(MDX_EINVAL, "%s: causal=%ld must be 0 or 1", op, (long)a->causal);

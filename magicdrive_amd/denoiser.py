@@ -93,8 +93,13 @@ class ConditioningBuffers:
     """Input-side device buffers of the conditioning prologue + the ops that turn them into the context tokens
     ehs_with_cam [B, 1+77+L, D] and the per-view map feature (BEVControlNetModel.forward :743-793, 842-850)."""
 
-    def __init__(self, bld: Builder, cn: PackedNet, cfg, n_scene: int, n_cam: int, L_box: int, latent_hw, n_text: int = 77):
+    def __init__(self, bld: Builder, cn: PackedNet, cfg, n_scene: int, n_cam: int, L_box: int, latent_hw, n_text: int = 77, dynamic: bool = False):
+        """dynamic: L_box is a box CAPACITY.  load() then takes boxes padded to any L <= L_box, fills the first L slots of every view (the
+        rest stay masked out: null embeddings, finite) and writes the live context length 1 + n_text + L to `self.live` (int32 [1]), which the
+        context attention reads on the device (ops.Attn.tk_dev)."""
         dev = bld.device
+        assert not dynamic or L_box > 0, "a dynamic plan needs a box capacity >= 1"
+        self.dynamic = bool(dynamic)
         H16 = bld.dtype                     # the plan's 16-bit activation type (bf16 or fp16)
         self.dtype = H16
         cc = cfg["controlnet"]; bb = cc["bbox"]
@@ -106,6 +111,7 @@ class ConditioningBuffers:
         self.n_text = n_text
         S = self.S
         self.ctx = torch.zeros(B, S, D, dtype=H16, device=dev)
+        self.live = torch.full((1,), S, dtype=torch.int32, device=dev)      # keys the context attention sees; < S only on a dynamic plan
         # camera: [B, 7, 3] fp32 (columns of the (3,7) matrix) -> Fourier 189 -> cam2token -> ctx[:, 0]
         ncol = cc["uncond_cam_in_dim"][1]
         F_cam = cc["cam_embedder_num_freqs"]
@@ -231,13 +237,27 @@ class ConditioningBuffers:
             if bb.shape[1] != nc:                               # view-shared boxes (unet_addon_rawbox.py:785-787)
                 assert bb.shape[1] == 1
                 bb = bb.expand(ns, nc, *bb.shape[2:]); cl = cl.expand(ns, nc, -1); mk = mk.expand(ns, nc, -1)
-            assert bb.shape[2] == self.L, f"boxes padded to {bb.shape[2]} but plan built for L={self.L}"
+            Lb = int(bb.shape[2])
+            dynamic = getattr(self, "dynamic", False)   # load() is also called unbound on bare stand-ins (tests/test_host.py), which predate the field
+            if dynamic:
+                assert 1 <= Lb <= self.L, f"boxes padded to {Lb} but the plan's box capacity is {self.L}"
+            else:
+                assert Lb == self.L, f"boxes padded to {Lb} but plan built for L={self.L}"
             bb = bb.to(self.box_in.device, F32)
             if self.minmax_normalize:          # normalizer('all-xyz'): (xyz - XYZ_MIN) / XYZ_RANGE (bbox_embedder.py:10-25, :175-176)
                 bb = (bb - bb.new_tensor([-200.0, -300.0, -20.0])) / bb.new_tensor([350.0, 650.0, 80.0])
-            self.box_in.copy_(bb.reshape(-1, *bb.shape[3:]))
-            self.box_cls.copy_(cl.to(self.box_cls.device, torch.int64).reshape(-1))
-            self.box_mask.copy_(mk.to(self.box_mask.device).reshape(-1).to(torch.uint8))
+            if Lb == self.L:
+                self.box_in.copy_(bb.reshape(-1, *bb.shape[3:]))
+                self.box_cls.copy_(cl.to(self.box_cls.device, torch.int64).reshape(-1))
+                self.box_mask.copy_(mk.to(self.box_mask.device).reshape(-1).to(torch.uint8))
+            else:                              # slots Lb .. capacity of every view: mask 0 -> null embeddings (finite), never attended to
+                B = ns * nc
+                self.box_in.zero_(); self.box_cls.zero_(); self.box_mask.zero_()
+                self.box_in.view(B, self.L, *bb.shape[3:])[:, :Lb].copy_(bb.reshape(B, Lb, *bb.shape[3:]))
+                self.box_cls.view(B, self.L)[:, :Lb].copy_(cl.to(self.box_cls.device, torch.int64).reshape(B, Lb))
+                self.box_mask.view(B, self.L)[:, :Lb].copy_(mk.to(self.box_mask.device).reshape(B, Lb).to(torch.uint8))
+            if dynamic:                        # an ordinary stream-ordered device write: no host sync, seen by the next replay
+                self.live.fill_(1 + self.n_text + Lb)
 
 
 def _emit_controlnet(bld: Builder, cn: PackedNet, x_in: torch.Tensor, cond: ConditioningBuffers, temb: TembTable, ctx_kv, h, w):
@@ -258,8 +278,13 @@ class SamplerPlan:
 
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
-                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False):
+                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes: bool = False):
+        """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
+        1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
+        from cond.live on the device.  Self and cross-view attention are untouched."""
         self.cfg, self.device = cfg, device
+        self.dynamic_boxes = bool(dynamic_boxes)
+        assert not dynamic_boxes or L_box > 0, "dynamic_boxes needs a box capacity >= 1 (calls without boxes keep their exact plan)"
         assert scheduler_kind in ("ddim", "unipc")
         assert given_view_mode in (0, 1, 2)
         self.scheduler_kind = scheduler_kind
@@ -290,7 +315,9 @@ class SamplerPlan:
             self.gv_cond = torch.zeros_like(self.x)
             self.gv_noise = torch.zeros_like(self.x)
         # ---------------- prologue ----------------
-        self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text)
+        self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text, dynamic=self.dynamic_boxes)
+        if self.dynamic_boxes:
+            bld.ctx_tk_dev = self.cond.live
         self.temb_cn = TembTable(cn, num_steps, device, per_sample=False)
         self.temb_un = TembTable(unet, num_steps, device, per_sample=False)
         self.temb_cn.sel = self.step_ctr

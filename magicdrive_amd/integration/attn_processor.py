@@ -24,7 +24,7 @@ _lib = None
 
 
 class MdxAttnDesc(ctypes.Structure):               # mirrors include/mdx.h MdxAttnDesc field for field
-    _fields_ = [(n, ctypes.c_void_p) for n in "Q K Vt O kvmap reserved_p".split()] + \
+    _fields_ = [(n, ctypes.c_void_p) for n in "Q K Vt O kvmap tk_dev".split()] + \
                [(n, ctypes.c_int64) for n in "B H Tq Tk d nsrc ldq sQ ldk sK ldv sV ldo sO".split()] + \
                [("scale", ctypes.c_double), ("joint", ctypes.c_int64), ("q_prescaled", ctypes.c_int64),   # q_prescaled = 0: plain Q
                 ("causal", ctypes.c_int64), ("v_rowmajor", ctypes.c_int64)]                                  # ABI 12; 0 / 0: no mask, V^T operand

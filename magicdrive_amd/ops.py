@@ -257,7 +257,9 @@ class Conv:
 @dataclass
 class Attn:
     """O = sum_s softmax(Q K_s^T * scale) V_s.  Q [B,Tq,C]; K [Bkv,Tk,C]; Vt [Bkv,C,ldv] (V transposed); O [B,Tq,C].
-    v_rowmajor: Vt is V itself, [B,Tk,C] (short sequences only: MdxAttnDesc.v_rowmajor); causal: query t sees keys 0..t."""
+    v_rowmajor: Vt is V itself, [B,Tk,C] (short sequences only: MdxAttnDesc.v_rowmajor); causal: query t sees keys 0..t.
+    tk_dev: int32 [1] on the device — Tk is then the CAPACITY of K / Vt and the kernel attends to the first tk_dev[0] keys, read when
+    it runs (MdxAttnDesc.tk_dev: the context attention of a sampler plan built for a bucket of box counts)."""
     Q: torch.Tensor
     K: torch.Tensor
     Vt: torch.Tensor
@@ -272,6 +274,7 @@ class Attn:
     q_prescaled: bool = False                # Q already carries scale * log2(e) (folded into to_q at pack time): probabilities are exp2(Q K^T - max)
     causal: bool = False
     v_rowmajor: bool = False
+    tk_dev: Optional[torch.Tensor] = None    # int32 [1], same device as Q: the live key count (<= Tk)
     opcode = L.OP_ATTN
 
     def lower(self):
@@ -301,6 +304,12 @@ class Attn:
         d.joint = int(self.joint)
         d.q_prescaled = int(self.q_prescaled)
         d.causal, d.v_rowmajor = int(self.causal), int(self.v_rowmajor)
+        if self.tk_dev is not None:
+            _chk(self.tk_dev.dtype == torch.int32 and self.tk_dev.numel() == 1 and self.tk_dev.device == Q.device,
+                 f"attn {self.name}: tk_dev must be one int32 on the device of Q")
+            _chk(self.nsrc == 1 and self.kvmap is None and not self.joint and not self.causal and not self.v_rowmajor,
+                 f"attn {self.name}: tk_dev serves one source, no joint softmax, no causal mask, the V^T operand")
+            d.tk_dev = _p(self.tk_dev)
         _chk(self.nsrc >= 1 and (self.nsrc <= 8 if self.joint else self.nsrc <= 2), f"attn {self.name}: nsrc={self.nsrc} (joint={self.joint})")
         return self.opcode, d
 

@@ -72,6 +72,12 @@ class StableDiffusionBEVControlNetPipeline:
         self.fork_max_scenes = 31
         self.fork_chunks = False                              # also fork inside every scene chunk of a multi-stream call (A/B switch: tools/streams_ab.py)
         self._side: Dict[Any, List[Any]] = {}
+        # One plan for a bucket of box counts.  The reference's validation flow pads the boxes of every batch to that batch's maximum, so the
+        # padded count L_box — part of the plan key — changes almost every call, and each new value builds a plan and captures its graphs.
+        # None (default): exact plans, keyed by L_box.  An integer n >= 1: a call with L_box > 0 uses the plan of capacity ceil(L_box / n) * n,
+        # built with SamplerPlan(dynamic_boxes=True) — the context attention reads the live key count from device memory, positions < L_box
+        # are computed as on the exact plan and the padded slots up to the capacity are never attended to.  Calls without boxes keep their plan.
+        self.box_bucket: Optional[int] = None
 
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
@@ -218,6 +224,18 @@ class StableDiffusionBEVControlNetPipeline:
         return out
 
     # ---- the sampler ----
+    def _box_plan_geometry(self, L_box: int):
+        """(box count the plan is built for, dynamic_boxes, the plan key's box entry) of a call whose boxes are padded to L_box, under
+        self.box_bucket.  The key entry is L_box itself — today's key — unless the plan is dynamic; then (capacity, "dynamic")."""
+        n = self.box_bucket
+        if n is None or L_box <= 0:
+            return int(L_box), False, int(L_box)
+        if isinstance(n, bool) or int(n) != n or int(n) < 1:
+            raise ValueError(f"box_bucket={n!r}: None or an integer >= 1")
+        n = int(n)
+        cap = -(-int(L_box) // n) * n
+        return cap, True, (cap, "dynamic")
+
     def _plan_config(self) -> Dict[str, Any]:
         """Architecture config of the sampler plan: the UNet's, with the conditioning encoders' geometry taken from the ControlNet."""
         cfg = dict(self.unet.cfg)
@@ -332,12 +350,14 @@ class StableDiffusionBEVControlNetPipeline:
 
         pdt = self.unet.packed().dtype
         fork = (n_chunk == 1 and 0 < b <= int(self.fork_max_scenes)) or (n_chunk > 1 and bool(self.fork_chunks))
+        L_plan, dyn_boxes, box_key = self._box_plan_geometry(L_box)
         plans = []
         for ci in range(n_chunk):
             s0, s1 = bounds[ci], bounds[ci + 1]
             # the packed nets' identity and 16-bit type are part of the key: `pipe.unet.to(torch.float16)` re-packs the weights, and a plan
             # built on the old PackedNet would keep running (and keep alive) the old ones
-            key = (s1 - s0, ci, do_cfg, L_box, h, w, n_steps, float(guidance_scale), float(controlnet_conditioning_scale), text.shape[1], sched_kind,
+            # box_bucket: the key carries (capacity, "dynamic") in the place of L_box; None / no boxes: today's key
+            key = (s1 - s0, ci, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(controlnet_conditioning_scale), text.shape[1], sched_kind,
                    gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
             plan = self._plans.get(key)
             if plan is None:
@@ -346,10 +366,10 @@ class StableDiffusionBEVControlNetPipeline:
                     # class / size, camera frequencies) is the ControlNet checkpoint's (a tiny or a 272x736 `...Plus` checkpoint loaded with
                     # from_pretrained would otherwise be planned with the SD-1.5 defaults)
                     plan_cfg = self._plan_config()
-                    plan = SamplerPlan(plan_cfg, self.unet.packed(), self.controlnet.packed(), device, s1 - s0, do_cfg, L_box, (h, w),
+                    plan = SamplerPlan(plan_cfg, self.unet.packed(), self.controlnet.packed(), device, s1 - s0, do_cfg, L_plan, (h, w),
                                        num_steps=n_steps, guidance_scale=guidance_scale,
                                        conditioning_scale=float(controlnet_conditioning_scale), n_text=text.shape[1], scheduler_kind=sched_kind,
-                                       given_view_mode=gv_mode, fork=fork)
+                                       given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes)
                     plan.compile()
                 self._plans.put(key, plan)
             plan.load_inputs(latents[s0:s1], rows(camera_param, s0, s1), rows(text, s0, s1), rows(image, s0, s1),

@@ -253,6 +253,8 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default=None, help="torch.distributed backend under torchrun (default: nccl = RCCL with a GPU, else gloo)")
     ap.add_argument("--reseed-per-run", action="store_true", help="deviation from the reference: an independent seed per (batch, validation run)")
     ap.add_argument("--cond-on-view", action="store_true", help="demo/run_cond_on_view.py: generation ti is sampled with the encoded ground-truth view ti given")
+    ap.add_argument("--box-bucket", type=int, default=None, help="one sampler plan per bucket of N padded box counts (pipe.box_bucket, INTEGRATION.md §1): the "
+                    "padded box count changes with almost every batch of a validation run; default: an exact plan per count")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args(argv)
     from magicdrive_amd.dataset import FolderSet
@@ -267,6 +269,10 @@ def main(argv=None):
         pipe = getattr(importlib.import_module(mod), fn)(a.ckpt, a.sd15, a.scheduler, device, a.cond_on_view)
     else:
         pipe = build_pipe(a.ckpt, a.sd15, a.scheduler, device, given_view=a.cond_on_view, hip_text_encoder=a.hip_text_encoder)
+    if a.box_bucket is not None:
+        if a.box_bucket < 1:
+            raise SystemExit("--box-bucket must be >= 1")
+        pipe.box_bucket = a.box_bucket
     data = FolderSet(a.data)
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
