@@ -209,6 +209,11 @@ int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream);
  *     blocks.py:112-121, 213-217 (left + right neighbour; the doubled out-bias is the caller's business);
  *   joint == 1, nsrc ∈ {1..8}: ONE softmax over the concatenation of the sources' keys — "concat" (the two neighbours, blocks.py:122-134)
  *     and "self" (all cameras of the scene, blocks.py:135-138).
+ *   Absent source slot (joint == 0 with a kvmap; camera rigs whose views have one neighbour or none — an open chain's end cameras, a camera
+ *     that overlaps nobody): kvmap[b*nsrc + s] < 0 means "query batch b has no source in slot s".  O of b is the sum over the slots that are
+ *     present; slot order does not matter ([a, -1] and [-1, a] give bit-identical O); with every slot absent (nsrc == 2: both, nsrc == 1: the
+ *     one) every O row of b is written as zeros.  A negative entry was an out-of-bounds read before, so no valid caller changes (ABI 12 stays).
+ *     Under joint == 1 a negative entry remains the caller's error (the reference's "concat" cannot be ragged: its torch.cat fails).
  * Requirements (host-checked, MDX_EINVAL, the message names the field):
  *   - d % 8 == 0, 0 < d <= 160.  Kernel instances exist for ceil(d / 16) in {1..6, 8, 10}, a ragged last 16-column chunk is masked:
  *     SUPPORTED d = 8 .. 96 (every multiple of 8), 120, 128, 152, 160;  d = 104, 112, 136, 144 return MDX_EUNSUPPORTED.

@@ -21,7 +21,8 @@
 //     the accumulator layout; V^T is read with the same permutation, so the sum is unchanged.
 //   * softmax in fp32 with exp2 and a folded log2(e)*scale; running max initialised to -inf.
 //   * nsrc == 2 (cross-view): the kv loop runs once per neighbour with its own softmax state and
-//     the two normalised outputs are summed in registers (blocks.py:213-217).
+//     the two normalised outputs are summed in registers (blocks.py:213-217).  A negative kvmap entry is an absent slot (a camera with
+//     one neighbour or none): the present sources are resolved once per workgroup, and a query batch without any writes zeros.
 #include "common.h"
 #include "launch.h"
 #include "options.h"
@@ -86,6 +87,23 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnParams p) {
     const int d = p.d;
     const int q = qb * (NW * 32) + wave * 32 + col;
 
+    // ---- the sources of this query batch (workgroup-uniform).  Separate softmax per source (joint == 0): a negative kvmap entry is an absent
+    // slot — the present ones are compacted (b0, then b1) and the loop runs n_eff of them.  None present: O rows of b are zeros; the whole
+    // workgroup leaves here, before the first barrier ----
+    int n_eff = p.nsrc, b0 = b, b1 = b;
+    if (!p.joint && p.kvmap) {
+        const int v0 = p.kvmap[b * p.nsrc], v1 = p.nsrc > 1 ? p.kvmap[b * p.nsrc + 1] : -1;
+        n_eff = (v0 >= 0) + (v1 >= 0);
+        b0 = v0 >= 0 ? v0 : v1; b1 = v1;
+        if (n_eff == 0) {
+            if (q < p.Tq) {
+                bf16_t* op = p.O + (long)b * p.sO + (long)q * p.ldo + (long)h * d;
+                for (int dd = 4 * half; dd < d; dd += 8) *(uint2*)(op + dd) = make_uint2(0u, 0u);
+            }
+            return;
+        }
+    }
+
     // ---- Q fragments (B operand of S^T = K Q^T): lane -> query column, 8 consecutive dims ----
     Frag8 qf[D16];
     {
@@ -114,8 +132,8 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnParams p) {
 
     float m_run = -INFINITY;
     float l_run = 0.f;
-    for (int s = 0; s < p.nsrc; ++s) {
-        const int bkv = p.kvmap ? p.kvmap[b * p.nsrc + s] : b;
+    for (int s = 0; s < n_eff; ++s) {
+        const int bkv = (p.joint && p.kvmap) ? p.kvmap[b * p.nsrc + s] : (s == 0 ? b0 : b1);
         const bf16_t* kbase = p.K + (long)bkv * p.sK + (long)h * d;
         const bf16_t* vbase = p.Vt + (long)bkv * p.sV + (long)h * d * p.ldv;
         if (!p.joint || s == 0) { m_run = -INFINITY; l_run = 0.f; }      // joint: the sources are ONE kv sequence (one softmax)

@@ -163,6 +163,14 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
             qb = idx % nq; b = bh / p.H; h = bh - b * p.H;
         }
     }
+    // ---- the kv sources of this query batch (workgroup-uniform: b comes from the workgroup index).  Their map entries are fetched HERE, first
+    // thing, and looked at only after the LDS image is zeroed (below): the fetch is one memory round trip per workgroup, and taken where
+    // the first source's descriptors are built (after the Q loads) it stood alone on the critical path of every workgroup's prologue.
+    int kv0 = b, kv1 = -1;
+    if (p.kvmap) {
+        kv0 = p.kvmap[b * p.nsrc];
+        if (!p.joint && p.nsrc > 1) kv1 = p.kvmap[b * p.nsrc + 1];
+    }
     int q0w = qb * (A2_NW * QW) + wave * QW;                 // this wave's first query
     // 32-query tiles of this wave that hold a real query (wave-uniform): the waves past Tq still stage and synchronise
     int nact = (p.Tq - q0w + 31) >> 5;
@@ -172,6 +180,29 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
 
     // ---- zero the LDS image once (pad rows / pad columns are never restaged), then the ones row ----
     for (int c = tid; c < (SCRATCH + 1024) / 16; c += A2_NT) *(uint4*)(smem + c * 16) = make_uint4(0, 0, 0, 0);
+    // Separate softmax per source (joint == 0): a negative kvmap entry is an absent slot (a camera with one neighbour or none).  The tile
+    // stream below is n_eff sources long (`total`): the issue cursor, the hand-counted vmcnt and the ring walk all count the PRESENT sources.
+    // kb0 = the first present one, used for the first descriptors only (nothing of this stays live across the tile loop: the kernel sits at
+    // the SGPR limit, and a value kept there is spilled to VGPR lanes and read back per tile); a second source is looked up when the stream
+    // reaches it, as ever.  None present: the workgroup writes its O rows as zeros and leaves HERE — all four waves together, before any
+    // LDS-DMA is issued and before the first barrier, so no wave waits for a piece or a barrier of another.
+    int n_eff = p.nsrc;
+    int kb0 = __builtin_amdgcn_readfirstlane(kv0);
+    if (!p.joint && p.kvmap) {
+        const int kb1 = __builtin_amdgcn_readfirstlane(kv1);
+        n_eff = (kb0 >= 0) + (kb1 >= 0);
+        if (kb0 < 0) kb0 = kb1;
+        if (n_eff == 0) {
+            constexpr int DC = D8 * 2;                         // 8-byte pieces of one query's head slice
+            const int qlo = RES ? 0 : qb * (A2_NW * 32 * QT);
+            const int qhi = RES ? p.Tq : min(p.Tq, qlo + A2_NW * 32 * QT);
+            for (int c = threadIdx.x; c < (qhi - qlo) * DC; c += A2_NT) {
+                const int r = c / DC, cc = c - r * DC;
+                *(uint2*)(p.O + (long)b * p.sO + (long)(qlo + r) * p.ldo + (long)h * (D8 * 8) + cc * 4) = make_uint2(0u, 0u);
+            }
+            return;
+        }
+    }
     __syncthreads();
     if (ONES) {
         for (int c = tid; c < A2_NBUF * 8; c += A2_NT) {       // row D of every buffer's V^T tile: 8 slots of 16 bytes (the swizzle permutes them within the row)
@@ -240,14 +271,15 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
         p_step[j] = __builtin_amdgcn_readfirstlane(p_step[j]);
     }
     a2_rsrc_t rs_p[PPW];           // the descriptor each piece loads through (K or V^T of the current source)
-    auto set_source = [&](int sidx) {
-        const int bkv = p.kvmap ? p.kvmap[b * p.nsrc + sidx] : b;
+    auto set_source_b = [&](int bkv) {
         const a2_rsrc_t rsK = a2_make_rsrc(p.K + (long)bkv * p.sK + (long)h * D);
         const a2_rsrc_t rsV = a2_make_rsrc(p.Vt + (long)bkv * p.sV + (long)h * D * p.ldv);
 #pragma unroll
         for (int j = 0; j < PPW; ++j) rs_p[j] = p_isk[j] ? rsK : rsV;
     };
-    const int total = ntile * p.nsrc;
+    // source sidx >= 1 of the stream: reached only when every slot up to it is present (the stream is n_eff sources long), so it is slot sidx
+    auto set_source = [&](int sidx) { set_source_b(p.kvmap[b * p.nsrc + sidx]); };
+    const int total = ntile * n_eff;       // tiles of the whole stream: the PRESENT sources only (issue cursor, vmcnt bookkeeping and the walk all count these)
     // issue tile `t` of the current source into ring slot `slot`
     auto issue = [&](int t, int slot) {
         const bool last = t == ntile - 1;                      // wave-uniform
@@ -471,7 +503,7 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
     }
     if constexpr (RES) {
         // ---- resident K / V^T: stage every tile of the (one) source once, then walk the query blocks ----
-        set_source(0);
+        set_source_b(kb0);
         for (int t = 0; t < ntile; ++t) issue(t, t);              // ntile <= A2_NBUF (launch_attn2)
         a2_wait_vmcnt<0>();
         __syncthreads();
@@ -552,7 +584,7 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
 
     // ---- prologue: tiles 0 and 1 of the stream in flight ----
     int ds = 0;                          // source the descriptors currently describe
-    set_source(0);
+    set_source_b(kb0);
     int it = 0, is_ = 0;                 // issue cursor: tile inside its source, source index
     auto issue_next = [&](int slot_) {
         if (is_ != ds) { set_source(is_); ds = is_; }
@@ -610,7 +642,7 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
         }                                                                                                              \
     }
 
-    for (int src = 0; src < p.nsrc; ++src) {
+    for (int src = 0; g < total; ++src) {                   // one round per PRESENT source: each consumes ntile tiles of the stream
         if (QT == 2 && nact == 2) A2_SOURCE(QT)
         else if (nact >= 1) A2_SOURCE(1)
         else A2_SOURCE(0)
@@ -619,7 +651,7 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
         if constexpr (PF) {
             // row 40 of O^T = sum of the (16-bit) probabilities: row tile 1, local row 8 -> register 4 of the lower half lanes
             const float inv = 1.0f / __shfl(oaccp[PF ? 1 : 0][4], col, 64);
-            if (TWO && src == 0) {                                // first neighbour done: park it (packed), restart the accumulators
+            if (TWO && g < total) {                               // another neighbour follows: park this one (packed), restart the accumulators
 #pragma unroll
                 for (int u = 0; u < 8; ++u) osum[0][u >> 2][(u >> 1) & 1][u & 1] = pack2bf(oaccp[0][2 * u] * inv, oaccp[0][2 * u + 1] * inv);
 #pragma unroll
@@ -629,21 +661,23 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
 #pragma unroll
                     for (int r = 0; r < 16; ++r) oaccp[PF ? rt : 0][r] = 0.f;
             } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) oaccp[0][r] *= inv;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) oaccp[PF ? 1 : 0][r] *= inv;
-                if (TWO) {
+                if (TWO && src > 0) {                             // something was parked: scale and add it back (one fma per element, as ever)
 #pragma unroll
                     for (int u = 0; u < 8; ++u) {
                         const unsigned w = osum[0][u >> 2][(u >> 1) & 1][u & 1];
-                        oaccp[0][2 * u] += bf2f((bf16_t)(w & 0xffffu)); oaccp[0][2 * u + 1] += bf2f((bf16_t)(w >> 16));
+                        oaccp[0][2 * u] = oaccp[0][2 * u] * inv + bf2f((bf16_t)(w & 0xffffu)); oaccp[0][2 * u + 1] = oaccp[0][2 * u + 1] * inv + bf2f((bf16_t)(w >> 16));
                     }
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         const unsigned w = osum[0][TWO ? 2 : 0][0][u];
-                        oaccp[PF ? 1 : 0][2 * u] += bf2f((bf16_t)(w & 0xffffu)); oaccp[PF ? 1 : 0][2 * u + 1] += bf2f((bf16_t)(w >> 16));
+                        oaccp[PF ? 1 : 0][2 * u] = oaccp[PF ? 1 : 0][2 * u] * inv + bf2f((bf16_t)(w & 0xffffu));
+                        oaccp[PF ? 1 : 0][2 * u + 1] = oaccp[PF ? 1 : 0][2 * u + 1] * inv + bf2f((bf16_t)(w >> 16));
                     }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) oaccp[0][r] *= inv;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) oaccp[PF ? 1 : 0][r] *= inv;
                 }
             }
             m_run[0] = FOLD ? 0.f : -INFINITY;
@@ -670,17 +704,16 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
                 for (int tq = 0; tq < 2; ++tq) {
                     const float inv = tq ? inv1 : inv0;
                     f32x4_t& a = oacc[qt][i][tq];
-                    if (TWO && src == 0) {                     // first neighbour done: park it, restart the accumulators
+                    if (TWO && g < total) {                    // another neighbour follows: park this one, restart the accumulators
                         osum[TWO ? qt : 0][TWO ? i : 0][tq][0] = pack2bf(a[0] * inv, a[1] * inv);
                         osum[TWO ? qt : 0][TWO ? i : 0][tq][1] = pack2bf(a[2] * inv, a[3] * inv);
                         a[0] = 0.f; a[1] = 0.f; a[2] = 0.f; a[3] = 0.f;
+                    } else if (TWO && src > 0) {               // something was parked: scale and add it back (one fma per element, as ever)
+                        const unsigned u0 = osum[TWO ? qt : 0][TWO ? i : 0][tq][0], u1 = osum[TWO ? qt : 0][TWO ? i : 0][tq][1];
+                        a[0] = a[0] * inv + bf2f((bf16_t)(u0 & 0xffffu)); a[1] = a[1] * inv + bf2f((bf16_t)(u0 >> 16));
+                        a[2] = a[2] * inv + bf2f((bf16_t)(u1 & 0xffffu)); a[3] = a[3] * inv + bf2f((bf16_t)(u1 >> 16));
                     } else {
                         a[0] *= inv; a[1] *= inv; a[2] *= inv; a[3] *= inv;
-                        if (TWO) {
-                            const unsigned u0 = osum[TWO ? qt : 0][TWO ? i : 0][tq][0], u1 = osum[TWO ? qt : 0][TWO ? i : 0][tq][1];
-                            a[0] += bf2f((bf16_t)(u0 & 0xffffu)); a[1] += bf2f((bf16_t)(u0 >> 16));
-                            a[2] += bf2f((bf16_t)(u1 & 0xffffu)); a[3] += bf2f((bf16_t)(u1 >> 16));
-                        }
                     }
                 }
             m_run[qt] = FOLD ? 0.f : -INFINITY; l_run[qt] = 0.f;

@@ -133,6 +133,24 @@ class PackedNet:
         b = self._get(("gateb", b1_scale), keys, lambda w1, b1, *a: (b1 * b1_scale if not a else gate(a) * b1 * b1_scale).contiguous().to(F32))
         return w, b
 
+    def folded_affine_rows(self, w2key, b2key, w1key, b1key, b1_scales: Sequence[float]):
+        """folded_affine with a bias PER ROW GROUP: (W2 W1, fp32 table [len(b1_scales), N], row r = W2 (s_r b1) + b2) — the cross-view out-bias of
+        a camera rig whose views have different neighbour counts (Builder.transformer_block)."""
+        keys = [w2key, b2key, w1key, b1key]
+        sc = tuple(float(x) for x in b1_scales)
+        w, _ = self.folded_affine(w2key, b2key, w1key, b1key, sc[0])
+        t = self._get(("foldrows",) + sc, keys, lambda w2, b2, w1, b1: torch.stack([w2 @ (b1 * f) + b2 for f in sc]).contiguous().to(F32))
+        return w, t
+
+    def gated_affine_rows(self, w1key, b1key, alpha_key: Optional[str], b1_scales: Sequence[float]):
+        """gated_affine with a bias per row group: row r = tanh(alpha) * (s_r b1) (alpha_key None: s_r b1)."""
+        keys = [w1key, b1key] + ([alpha_key] if alpha_key else [])
+        sc = tuple(float(x) for x in b1_scales)
+        w, _ = self.gated_affine(w1key, b1key, alpha_key, sc[0])
+        t = self._get(("gaterows",) + sc, keys,
+                      lambda w1, b1, *a: torch.stack([b1 * f if not a else torch.tanh(a[0].reshape(-1)) * b1 * f for f in sc]).contiguous().to(F32))
+        return w, t
+
     def table(self, key):                              # 2-D bf16 table (class tokens)
         return self._get("table", [key], lambda t: t.contiguous().to(self.dtype))
 
@@ -295,25 +313,45 @@ class Builder:
         pair = cfg["neighboring_view_pair"]
         pair = {int(k): [int(x) for x in v] for k, v in pair.items()}
         # cross-view attention form (BasicMultiviewTransformerBlock._construct_attn_input, blocks.py:106-142):
-        #   add    (default): one attention per (view, neighbour), outputs summed -> 2 sources, separate softmax, to_out bias twice
+        #   add    (default): one attention per (view, neighbour), outputs summed -> <= 2 sources per view, separate softmax, to_out bias once
+        #                     per neighbour.  Any rig: a view may list 0, 1 or 2 neighbours (an open chain's end cameras, a camera that overlaps
+        #                     nobody); a missing slot is -1 in the kv map (MdxAttnDesc: absent source) and a view without neighbours gets zeros.
         #   concat : the neighbours' tokens concatenated into one kv sequence     -> 2 sources, ONE softmax, bias once
         #   self   : all cameras of the scene as one sequence (queries of every view see every view) -> n_cam sources, ONE softmax, bias once
         self.nattn = cfg.get("neighboring_attn_type", "add")
         if self.nattn not in ("add", "concat", "self"):
             raise NotImplementedError(f"Unknown type: {self.nattn}")          # the reference's error (blocks.py:139-141)
+        counts = [len(pair[c]) for c in range(n_cam)]
+        # neighbours per view (all n_views of them) where they DIFFER between the views of the rig, else None: the out-bias of attn4 is then a
+        # per-view table instead of one vector (transformer_block)
+        self.xv_counts: Optional[List[int]] = None
+        self.xv_bo_scale = 1.0                                                    # concat / self: ONE attention per view, its out-bias once
+        if self.nattn == "add":
+            for c, n in enumerate(counts):
+                if n > 2:
+                    raise NotImplementedError(f"neighboring_attn_type 'add': view {c} lists {n} neighbours; the summed cross-view form handles at most 2 per view")
+            if max(counts) == 0:       # the reference cannot run this either: torch.cat of an empty list (blocks.py:119)
+                raise RuntimeError("neighboring_view_pair lists no neighbour for any view: there is no cross-view attention to run (torch.cat(): expected a non-empty list of Tensors)")
+            self.xv_nsrc = 1 if all(n == 1 for n in counts) else 2
+            if len(set(counts)) == 1:
+                self.xv_bo_scale = float(counts[0])                               # the same count everywhere: count * b_o is one vector (the ring: 2 b_o)
+            else:
+                self.xv_counts = [counts[i % n_cam] for i in range(n_views)]
+        elif self.nattn == "concat":
+            if len(set(counts)) != 1 or counts[0] == 0:
+                raise RuntimeError(f"neighboring_attn_type 'concat' needs the same, non-zero number of neighbours for every view (got {counts}): "
+                                   "the reference's torch.cat of the per-view kv sequences fails too (blocks.py:125-132)")
+            self.xv_nsrc = counts[0]
+        else:
+            self.xv_nsrc = n_cam
+        assert self.xv_nsrc <= 8, "joint cross-view attention handles <= 8 sources"
         kv = []
         for i in range(n_views):
             base = (i // n_cam) * n_cam
             srcs = list(range(n_cam)) if self.nattn == "self" else pair[i % n_cam]
-            for nb in srcs:
-                kv.append(base + nb)
-        if self.nattn == "add":
-            assert all(len(v) == 2 for v in pair.values()), "the summed cross-view form handles exactly 2 neighbours per view"
-        else:
-            assert len({len(v) for v in pair.values()}) == 1 and (self.nattn == "self" or len(pair[0]) <= 8), "concat / self: equal source counts, <= 8"
-        self.xv_nsrc = n_cam if self.nattn == "self" else len(pair[0])
-        assert self.xv_nsrc <= 8, "joint cross-view attention handles <= 8 sources"
+            kv += [base + nb for nb in srcs] + [-1] * (self.xv_nsrc - len(srcs))  # -1: absent slot (add mode only)
         self.kvmap = torch.tensor(kv, dtype=torch.int32, device=device)
+        self.kvmap._mdx_present = sum(1 for x in kv if x >= 0)                    # (view, source) pairs really attended: flops.op_flops
 
     # ---- small helpers ---------------------------------------------------------------
     def emit(self, op):
@@ -480,7 +518,9 @@ class Builder:
                          name=name + ".attn2"))
         self.pool.put(q2)
         has4 = net.has(pre + "attn4.to_q.weight")
-        fold3 = fuse_ln and self.FOLD_NORM3
+        # a rig with mixed neighbour counts adds attn4's out-bias through the GEMM's temb table, which the statistics-emitting route does not take:
+        # such a block keeps the LayerNorm pass in front of its GEGLU
+        fold3 = fuse_ln and self.FOLD_NORM3 and not (has4 and self.xv_counts is not None)
         s2 = self.rowstat(M) if (fuse_ln and (has4 or fold3)) else None       # read by norm4 (multiview blocks) or, folded, by norm3 (ControlNet blocks)
         h2 = self.gemm(ao2, net.lin(pre + "attn2.to_out.0.weight"), C, bias=net.vec(pre + "attn2.to_out.0.bias"), R=h1, rowstat=s2, name=name + ".attn2.out")
         self.pool.put(ao2); self.pool.put(h1)
@@ -497,14 +537,25 @@ class Builder:
             self.pool.put(n4)
             # connector(to_out(o_l + o_r) + 2 b_o) is one affine map: fold it at pack time,
             #   W = W_c W_o ,  b = W_c (2 b_o) + b_c     (one GEMM instead of two per block; fp32 fold, bf16 weights)
-            bo_scale = 2.0 if self.nattn == "add" else 1.0                        # concat / self: ONE attention per view, its out-bias once
-            if net.has(pre + "connector.weight"):                                 # zero_module_type zero_linear (blocks.py:81-83)
-                wf, bf_ = net.folded_affine(pre + "connector.weight", pre + "connector.bias", pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias", bo_scale)
-            else:                                                                 # gated: tanh(alpha) per channel (blocks.py:24-32, 84-85); none: identity (:86-88)
-                wf, bf_ = net.gated_affine(pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias",
-                                           pre + "connector.alpha" if net.has(pre + "connector.alpha") else None, bo_scale)
-            s3 = self.rowstat(M) if fold3 else None
-            h3 = self.gemm(ao4, wf, C, bias=bf_, R=h2, rowstat=s3, name=name + ".attn4.out+connector")
+            # add mode: the out-bias once per neighbour of the view (the ring: 2 b_o).  The same count for every view: one bias vector.  Mixed counts
+            # (an open chain, a camera without neighbours): an fp32 table [n_views][C], row v = W_c (count(v) b_o) + b_c, added per T rows (temb)
+            bo_scale = self.xv_bo_scale
+            zero_linear = net.has(pre + "connector.weight")                       # zero_module_type zero_linear (blocks.py:81-83)
+            alpha_key = pre + "connector.alpha" if net.has(pre + "connector.alpha") else None   # gated: tanh(alpha) per channel (blocks.py:24-32, 84-85); none: identity (:86-88)
+            if self.xv_counts is not None:
+                if zero_linear:
+                    wf, tab = net.folded_affine_rows(pre + "connector.weight", pre + "connector.bias", pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias", self.xv_counts)
+                else:
+                    wf, tab = net.gated_affine_rows(pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias", alpha_key, self.xv_counts)
+                s3 = None
+                h3 = self.gemm(ao4, wf, C, temb=tab, temb_b_stride=C, rows_per_b=T, R=h2, name=name + ".attn4.out+connector")
+            else:
+                if zero_linear:
+                    wf, bf_ = net.folded_affine(pre + "connector.weight", pre + "connector.bias", pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias", bo_scale)
+                else:
+                    wf, bf_ = net.gated_affine(pre + "attn4.to_out.0.weight", pre + "attn4.to_out.0.bias", alpha_key, bo_scale)
+                s3 = self.rowstat(M) if fold3 else None
+                h3 = self.gemm(ao4, wf, C, bias=bf_, R=h2, rowstat=s3, name=name + ".attn4.out+connector")
             self.pool.put(ao4); self.pool.put(h2)
         else:
             h3 = h2

@@ -42,6 +42,12 @@ def op_flops(op) -> float:
         return 2.0 * B * Ho * Wo * Cout * kh * kw * Cin
     if isinstance(op, O.Attn):
         B, Tq, C = op.Q.shape
+        if op.kvmap is not None and not op.joint:          # summed cross-view form: a negative kv map entry is an absent source — count the pairs attended
+            present = getattr(op.kvmap, "_mdx_present", None)
+            if present is None:
+                present = int((op.kvmap >= 0).sum())
+            if present != B * op.nsrc:
+                return 4.0 * present * Tq * op.Tk * C
         return 4.0 * B * Tq * op.Tk * C * op.nsrc          # QK^T + PV
     return 0.0
 

@@ -28,6 +28,19 @@ _ARCH_KEYS = ("in_channels", "out_channels", "flip_sin_to_cos", "freq_shift", "d
               "block_out_channels", "layers_per_block", "norm_num_groups", "norm_eps", "cross_attention_dim", "attention_head_dim")
 
 
+def check_view_pair(pair: Dict) -> None:
+    """A camera rig as the reference reads it (blocks.py:102-121): view v of a scene is key v, so the keys are exactly 0..n-1 and every
+    neighbour names one of them.  ValueError when the config is loaded — not an index error inside a plan build."""
+    n = len(pair)
+    keys = sorted(int(k) for k in pair)
+    if keys != list(range(n)):
+        raise ValueError(f"neighboring_view_pair: the keys must be exactly 0..{n - 1} (one per camera), got {keys}")
+    for k, v in pair.items():
+        bad = [int(x) for x in v if not 0 <= int(x) < n]
+        if bad:
+            raise ValueError(f"neighboring_view_pair: view {k} names neighbour(s) {bad} outside 0..{n - 1}")
+
+
 def arch_config_from_json(js: Dict, base: Optional[Dict] = None) -> Dict:
     """diffusers config.json -> our cfg dict (unknown keys ignored, missing keys = SD-1.5 defaults)."""
     cfg = copy.deepcopy(base or spec.SD15_CONFIG)
@@ -37,6 +50,7 @@ def arch_config_from_json(js: Dict, base: Optional[Dict] = None) -> Dict:
             cfg[k] = tuple(v) if isinstance(v, list) else v
     if js.get("neighboring_view_pair"):
         cfg["neighboring_view_pair"] = {int(k): [int(x) for x in v] for k, v in js["neighboring_view_pair"].items()}
+        check_view_pair(cfg["neighboring_view_pair"])
     for k in ("neighboring_attn_type", "zero_module_type"):
         if k in js:
             cfg[k] = js[k]
@@ -98,7 +112,10 @@ class MdxModel:
 
     def __init__(self, cfg: Dict, state_dict: Dict[str, torch.Tensor], torch_dtype=torch.bfloat16):
         self.cfg = copy.deepcopy(cfg)
-        shapes = type(self)._shape_fn(self.cfg)
+        if self.cfg.get("neighboring_view_pair"):          # from_config hands a cfg dict over directly: the same check as arch_config_from_json
+            self.cfg["neighboring_view_pair"] = {int(k): [int(x) for x in v] for k, v in self.cfg["neighboring_view_pair"].items()}
+            check_view_pair(self.cfg["neighboring_view_pair"])
+        shapes =type(self)._shape_fn(self.cfg)
         missing = [k for k in shapes if k not in state_dict]
         if missing:
             raise KeyError(f"{type(self).__name__}: state dict lacks {len(missing)} tensors, e.g. {missing[:4]}")

@@ -24,7 +24,7 @@ Fixtures
   tiny_vae_decode.pt  diffusers AutoencoderKL.decode (the reference's `vae`, pipeline_bev_controlnet.py:100-112) of a tiny decoder config
                     (spec.VAE_TINY_CONFIG, seeded weights) on 2 latents of 7x13.
 
-`python tools/make_golden.py unipc` / `... hires` / `... given` / `... vae` / `... nattn` / `... zmod` regenerate only that fixture.
+`python tools/make_golden.py unipc` / `... hires` / `... given` / `... vae` / `... nattn` / `... zmod` / `... rig` regenerate only that fixture.
 
 Round 4:
   tiny_pipeline_given_view_unipc.pt `... givenunipc`  the given-view pipeline with UniPC — the scheduler demo/run_cond_on_view.py's
@@ -48,6 +48,9 @@ weights the HIP model holds — so that the fixture measures arithmetic, not wei
                     plain BEVControlNetConditioningEmbedding (tiny width).
   tiny_forward_nattn.pt  the reference UNet forward with neighboring_attn_type = concat and = self (same tiny weights and inputs).
   tiny_forward_zmod.pt   the reference UNet forward with zero_module_type = gated (GatedConnector) and = none (identity connector).
+  tiny_forward_rig.pt / tiny_pipeline_rig.pt `... rig`  camera rigs that are not a ring (neighboring_view_pair with one or no neighbour per
+                    view): the reference UNet forward on a five-camera open chain and on an asymmetric three-camera rig, and the reference
+                    pipeline __call__ on the chain (CFG, 3 boxes, 4 DDIM steps).
   tiny_reference_checks.pt `... refchecks`  parameter shapes of the tiny reference modules; the reference pipeline's refusal of the stock
                     DDIMScheduler (error, message, step() parameters); the reference UniPCMultistepScheduler on a
                     fixed pseudo-model for four (steps, order, solver type) cases — what the oracle tests compare against without the reference.
@@ -321,6 +324,44 @@ def zmod_fixture(out_dir, cfg0, csd, meta, hw=(28, 50)):
     torch.save(out, os.path.join(out_dir, "tiny_forward_zmod.pt"))
 
 
+RIGS = {"chain5": {0: [1], 1: [0, 2], 2: [1, 3], 3: [2, 4], 4: [3]},       # five-camera open chain: the end cameras have one neighbour
+        "asym3": {0: [1, 2], 1: [0], 2: []}}                                 # an empty list; not symmetric under any relabelling
+
+
+def rig_fixture(out_dir, cfg0, usd, csd, meta, hw=(28, 50)):
+    """neighboring_view_pair with 0, 1 or 2 neighbours per view in the default `add` mode (blocks.py:106-121 emits one attention per
+    (view, neighbour) pair, :213-217 sums per view what came back — nothing for an empty list): the UNet forward of the REAL reference on
+    the same tiny weights per rig, and the reference pipeline __call__ on the chain.  n_cam = number of keys of the rig."""
+    out = {"meta": meta, "rigs": RIGS, "lat_seed": {"chain5": 23, "asym3": 29}, "timesteps": {"chain5": torch.tensor([430]), "asym3": torch.tensor([710])},
+           "scene_seed": 1234, "boxes": 3}
+    for name, rig in RIGS.items():
+        n = len(rig)
+        cfg = dict(cfg0); cfg["neighboring_view_pair"] = rig
+        ns, unet, cnet = ref_models.build_reference(cfg, usd, csd)
+        sc = scene(cfg, 1, 3, hw, n_cam=n)
+        lat = torch.randn(1, n, 4, *hw, generator=torch.Generator().manual_seed(out["lat_seed"][name]))
+        t = out["timesteps"][name]
+        with torch.no_grad():
+            d, m, ctx = cnet(lat, t, sc["camera_param"], sc["bboxes_3d_data"], sc["prompt_embeds"], sc["bev_map"], return_dict=False)
+            e = unet(lat.reshape(-1, 4, *hw), t.repeat_interleave(n), encoder_hidden_states=ctx,
+                     down_block_additional_residuals=d, mid_block_additional_residual=m).sample
+        out["eps_" + name] = e.half()
+        print("tiny_forward_rig", name, "eps std", e.std().item())
+    torch.save(out, os.path.join(out_dir, "tiny_forward_rig.pt"))
+
+    cfg = dict(cfg0); cfg["neighboring_view_pair"] = RIGS["chain5"]
+    ns, pipe = ref_models.build_reference_pipeline(cfg, usd, csd)
+    sc = scene(cfg, 2, 3, hw, n_cam=5)
+    with torch.no_grad():
+        x = pipe(prompt=None, image=sc["bev_map"], camera_param=sc["camera_param"], height=224, width=400, num_inference_steps=4,
+                 guidance_scale=2.0, latents=sc["latents"].clone(), prompt_embeds=sc["prompt_embeds"],
+                 negative_prompt_embeds=sc["negative_prompt_embeds"], output_type="latent",
+                 bev_controlnet_kwargs={"bboxes_3d_data": sc["bboxes_3d_data"]}).images
+    torch.save({"meta": meta, "rig": RIGS["chain5"], "scenes": 2, "boxes": 3, "scene_seed": 1234, "steps": 4, "guidance": 2.0, "latents_cfg": x.clone()},
+               os.path.join(out_dir, "tiny_pipeline_rig.pt"))
+    print("tiny_pipeline_rig: |x|", x.abs().mean().item(), tuple(x.shape))
+
+
 def _trace_cb(store, every):
     def cb(i, t, latents):
         if (i + 1) % every == 0:
@@ -520,6 +561,8 @@ def main():
         return nattn_fixture(out_dir, cfg, usd, csd, meta)
     if sys.argv[1:] == ["zmod"]:
         return zmod_fixture(out_dir, cfg, csd, meta)
+    if sys.argv[1:] == ["rig"]:
+        return rig_fixture(out_dir, cfg, usd, csd, meta)
     if sys.argv[1:] in (["res272"], ["res424"]):
         return resolution_fixture(out_dir, cfg, usd, meta, "272x736" if sys.argv[1] == "res272" else "424x800")
 
