@@ -244,6 +244,13 @@ int mdx_conv2d_direct(const MdxConvDirectDesc* d, void* stream);
  *       - d in {16, 32, 40, 80, 160};  any other d returns MDX_EUNSUPPORTED.
  *       - alignment / strides: as for the V^T form above (ldq, ldk, ldv, sQ, sK, sV multiples of 8; Q, K, Vt 16-byte, O 8-byte aligned;
  *         ldo, sO multiples of 4); B * H * ceil(Tq / 128) must fit a 32-bit int.
+ * One key count per query batch (mdx_attention_ctx_rows_bf16 / _f16, MDX_OP_ATTN_ROWS; additive symbols, the ABI version stays 12).  The
+ * SAME descriptor, read differently in one field: tk_dev points to int32 [B] and batch b of Q attends to keys 0 .. tk_dev[b]-1 of batch b of
+ * K / V^T - the scenes of a batched call attend to their own boxes, as each would in a call of its own.  Everything of the tk_dev paragraph
+ * above holds per batch: counts are read when the kernel runs, the work of a workgroup depends on its own batch's count only (O of a batch is
+ * bit-identical to mdx_attention_* with that count on that batch alone), and a count outside [1, Tk] writes NaN to the O rows of THAT batch.
+ *   - tk_dev == NULL, kvmap != NULL, nsrc != 1, joint, causal or v_rowmajor != 0 return MDX_EINVAL (the message names the field); d, alignment
+ *     and strides as in the tk_dev paragraph.  mdx_attention_* itself never reads more than one count.
  */
 typedef struct MdxAttnDesc {
     const void* Q; const void* K; const void* Vt; void* O;
@@ -259,6 +266,7 @@ typedef struct MdxAttnDesc {
     int64_t v_rowmajor;    /* ABI 12.  1: `Vt` holds V row-major [Bkv][Tk][H*d] with token stride ldv (short-sequence kernel).  0: V^T as above. */
 } MdxAttnDesc;
 int mdx_attention_bf16(const MdxAttnDesc* d, void* stream);
+int mdx_attention_ctx_rows_bf16(const MdxAttnDesc* d, void* stream);
 
 /*
  * mdx_groupnorm_bf16 — GroupNorm(+SiLU) over channels-last [B][HW][C]
@@ -446,6 +454,7 @@ int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream);
 #define MDX_OP_DDIM 11
 #define MDX_OP_UNIPC 12
 #define MDX_OP_SOFTMAX 13
+#define MDX_OP_ATTN_ROWS 14   /* MdxAttnDesc through mdx_attention_ctx_rows_*: tk_dev -> int32 [B] */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -475,6 +484,7 @@ int mdx_timestep_embedding_f16(const MdxTimeEmbDesc* d, void* stream);
 int mdx_cfg_ddim_step_f16(const MdxDdimDesc* d, void* stream);
 int mdx_cfg_unipc_step_f16(const MdxUniPCDesc* d, void* stream);
 int mdx_softmax_rows_f16(const MdxSoftmaxDesc* d, void* stream);
+int mdx_attention_ctx_rows_f16(const MdxAttnDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -25,6 +25,9 @@
 //   * n < 1 or n > Tk cannot raise without a sync: n is clamped to [1, Tk] for addressing and every O row is written as NaN — the
 //     loud-miss convention of the DDIM kernel's step index -1.
 //   * all of Q / K / V^T / O addressing is 64-bit (batch and row offsets as long).
+//   * per-batch form (attn_ctx_rows_kernel, entry points mdx_attention_ctx_rows_*): the same body with n = tk_dev[b] for the workgroup's
+//     query batch b — a batched call whose scenes carry different box counts (SamplerPlan dynamic_boxes="scene"): each scene attends to
+//     its own boxes as in a one-scene call.  A bad count poisons the O rows of its own batch only.
 // LDS strides are attention.hip's (K rows d16 * 16 + 8 elements, V^T rows 64 + 4 elements): its header states both fragment reads
 // conflict-free.  For THIS kernel that is taken over from the bank rule (bank = dword address % 64, per 32-lane half), i.e. computed, NOT
 // measured: no LDS-conflict counter of this kernel is on file, and correctness does not depend on it.
@@ -50,200 +53,29 @@ constexpr unsigned CTX_NAN2 = 0x7E007E00u;   // two quiet NaNs of the 16-bit typ
 constexpr unsigned CTX_NAN2 = 0x7FC07FC0u;
 #endif
 
+// One count for the whole launch (*tk_dev), or one per query batch (tk_dev[b], int32 [B]): the per-scene box counts of a batched call
+// (denoiser.SamplerPlan dynamic_boxes="scene").  Workgroups of one rows launch walk different tile counts, and nothing a workgroup does
+// depends on another batch's count.  Everything but the load of the count is the same text (attn_ctx_body.h).
 template <int D>
 __global__ __launch_bounds__(CTX_NW * 64) void attn_ctx_kernel(AttnCtxParams p) {
-    constexpr int D16 = (D + 15) / 16;  // 16-column chunks of QK^T (a ragged last chunk is zero-filled)
-    constexpr int DT = (D16 + 1) / 2;   // 32-row d tiles of O^T
-    constexpr int DP = D16 * 16;        // padded head dim for QK^T
-    constexpr int KSTR = DP + 8;        // K LDS row stride (elements)
-    constexpr int NT = CTX_NW * 64;
-    constexpr int KTOT = CTX_KVT * (DP / 8), VTOT = DT * 32 * (CTX_KVT / 8);   // 16-byte chunks per K / V^T tile
-    constexpr int KCH = (KTOT + NT - 1) / NT, VCH = (VTOT + NT - 1) / NT;      // chunks per thread (d = 160: 5 + 5)
-    static_assert(D % 8 == 0 && D <= 160, "head dim");
-    __shared__ __attribute__((aligned(16))) bf16_t Ks[CTX_KVT * KSTR];
-    __shared__ __attribute__((aligned(16))) bf16_t Vs[DT * 32 * CTX_VSTR];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int half = lane >> 5;
-    const int col = lane & 31;
-    const int bh = blockIdx.x / p.qblocks, qb = blockIdx.x - bh * p.qblocks;
-    const int b = bh / p.H, h = bh - b * p.H;
-    const int q = qb * (CTX_NW * 32) + wave * 32 + col;
-
-    // ---- the live key count: one load per workgroup, wave-uniform; out of range -> clamped for addressing, O = NaN ----
-    const int n_raw = __builtin_amdgcn_readfirstlane(*p.tk_dev);
-    const bool bad = n_raw < 1 || n_raw > p.Tk;
-    const int n = min(max(n_raw, 1), p.Tk);
-
-    // ---- Q fragments (B operand of S^T = K Q^T): lane -> query column, 8 consecutive dims ----
-    Frag8 qf[D16];
-    {
-        const bf16_t* qp = p.Q + (long)b * p.sQ + (long)(q < p.Tq ? q : 0) * p.ldq + (long)h * D;
-#pragma unroll
-        for (int ks = 0; ks < D16; ++ks) {
-            const int dd = ks * 16 + half * 8;
-            uint4 v = make_uint4(0, 0, 0, 0);
-            if (q < p.Tq && dd < D) v = *(const uint4*)(qp + dd);
-            qf[ks].u = v;
-        }
-    }
-
-    f32x16_t oacc[DT];
-#pragma unroll
-    for (int i = 0; i < DT; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
-    float m_run = -INFINITY;
-    float l_run = 0.f;
-    const bf16_t* kbase = p.K + (long)b * p.sK + (long)h * D;
-    const bf16_t* vbase = p.Vt + (long)b * p.sV + (long)h * D * p.ldv;
-
-    for (int j0 = 0; j0 < n; j0 += CTX_KVT) {
-        uint4 kreg[KCH];
-        Frag8 vreg[VCH];
-#pragma unroll
-        for (int i = 0; i < KCH; ++i) {
-            const int c = tid + i * NT;
-            const int row = c / (DP / 8);
-            const int cc = c - row * (DP / 8);
-            const bool ok = c < KTOT && j0 + row < n && cc * 8 < D;
-            const int rr = min(j0 + row, n - 1), cq = min(cc * 8, D - 8);
-            const uint4 v = *(const uint4*)(kbase + (long)rr * p.ldk + cq);
-            kreg[i] = ok ? v : make_uint4(0, 0, 0, 0);
-        }
-#pragma unroll
-        for (int i = 0; i < VCH; ++i) {
-            const int c = tid + i * NT;
-            const int row = c >> 3;
-            const int kv0 = j0 + (c & 7) * 8;
-            const bool ok = c < VTOT && row < D && kv0 < n;
-            Frag8 v;
-            // kv0 < n <= Tk <= ldv and both kv0 and ldv are multiples of 8: the 16 bytes at kv0 lie inside the row
-            v.u = *(const uint4*)(vbase + (long)min(row, D - 1) * p.ldv + (kv0 < n ? kv0 : 0));
-            if (!ok) v.u = make_uint4(0, 0, 0, 0);
-            vreg[i] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < KCH; ++i) {
-            const int c = tid + i * NT;
-            const int row = c / (DP / 8);
-            const int cc = c - row * (DP / 8);
-            if (c < KTOT) *(uint4*)(Ks + row * KSTR + cc * 8) = kreg[i];
-        }
-#pragma unroll
-        for (int i = 0; i < VCH; ++i) {
-            const int c = tid + i * NT;
-            if (c < VTOT) {
-                Frag8 v = vreg[i];
-                const int kv0 = j0 + (c & 7) * 8;
-                if (kv0 + 8 > n) {              // columns >= n: other tokens' data or pad — zeroed by select, never multiplied
-#pragma unroll
-                    for (int e = 0; e < 8; ++e)
-                        if (kv0 + e >= n) v.h[e] = 0;
-                }
-                uint2* dst = (uint2*)(Vs + (c >> 3) * CTX_VSTR + (c & 7) * 8);
-                dst[0] = v.d2[0];
-                dst[1] = v.d2[1];
-            }
-        }
-        __syncthreads();
-
-        // ---- S^T[kv][q] for two 32-kv sub-tiles ----
-        f32x16_t sacc[2];
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc[sub][r] = 0.f;
-            const bf16_t* kr = Ks + (sub * 32 + col) * KSTR + half * 8;
-#pragma unroll
-            for (int ks = 0; ks < D16; ++ks) {
-                Frag8 kf;
-                kf.u = *(const uint4*)(kr + ks * 16);
-                sacc[sub] = MDX_MFMA_32x32x16(kf.v, qf[ks].v, sacc[sub]);
-            }
-        }
-        // ---- online softmax (this lane: one query, 32 of the 64 kv) ----
-        if (j0 + CTX_KVT > n) {                 // only the last tile has kv >= n to mask (wave-uniform branch)
-#pragma unroll
-            for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int kv = j0 + sub * 32 + mfma32_row(r, lane);
-                    if (kv >= n) sacc[sub][r] = -INFINITY;
-                }
-        }
-        float mx = -INFINITY;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[sub][r]);
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64)) * p.scale_log2;
-        const float m_new = fmaxf(m_run, mx);       // finite: every tile has >= 1 valid kv (j0 < n)
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);   // exp2(-inf) = 0 on the first tile
-        m_run = m_new;
-        float psum = 0.f;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(sacc[sub][r], p.scale_log2, -m_new));
-                sacc[sub][r] = pv;
-                psum += pv;
-            }
-        l_run = l_run * alpha + psum;
-#pragma unroll
-        for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
-
-        // ---- O^T[dd][q] += V^T[dd][kv] * P^T[kv][q] ----
-#pragma unroll
-        for (int kstep = 0; kstep < 4; ++kstep) {
-            const int sub = kstep >> 1, kk = kstep & 1;
-            Frag8 pf;
-            pf.u.x = pack2bf(sacc[sub][kk * 8 + 0], sacc[sub][kk * 8 + 1]);
-            pf.u.y = pack2bf(sacc[sub][kk * 8 + 2], sacc[sub][kk * 8 + 3]);
-            pf.u.z = pack2bf(sacc[sub][kk * 8 + 4], sacc[sub][kk * 8 + 5]);
-            pf.u.w = pack2bf(sacc[sub][kk * 8 + 6], sacc[sub][kk * 8 + 7]);
-            const bf16_t* vr = Vs + col * CTX_VSTR + kstep * 16 + 4 * half;
-#pragma unroll
-            for (int i = 0; i < DT; ++i) {
-                Frag8 vf;
-                vf.d2[0] = *(const uint2*)(vr + i * 32 * CTX_VSTR);
-                vf.d2[1] = *(const uint2*)(vr + i * 32 * CTX_VSTR + 8);
-                oacc[i] = MDX_MFMA_32x32x16(vf.v, pf.v, oacc[i]);
-            }
-        }
-        __syncthreads();
-    }
-    const float inv = 1.0f / (l_run + __shfl_xor(l_run, 32, 64));
-
-    // ---- store O[q][h*d + dd]: lane has 4 consecutive dd per register group ----
-    if (q < p.Tq) {
-        bf16_t* op = p.O + (long)b * p.sO + (long)q * p.ldo + (long)h * D;
-#pragma unroll
-        for (int i = 0; i < DT; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int dd = i * 32 + 8 * g + 4 * half;
-                if (dd < D) {
-                    uint2 ov;
-                    ov.x = pack2bf(oacc[i][4 * g] * inv, oacc[i][4 * g + 1] * inv);
-                    ov.y = pack2bf(oacc[i][4 * g + 2] * inv, oacc[i][4 * g + 3] * inv);
-                    if (bad) ov = make_uint2(CTX_NAN2, CTX_NAN2);
-                    *(uint2*)(op + dd) = ov;
-                }
-            }
-    }
+#define CTX_LIVE_COUNT (*p.tk_dev)
+#include "attn_ctx_body.h"
+#undef CTX_LIVE_COUNT
 }
 
 template <int D>
-static int launch_attn_ctx(const AttnCtxParams& p, long blocks, bool pre, hipStream_t st) {
-    hipLaunchKernelGGL((attn_ctx_kernel<D>), dim3((unsigned)blocks), dim3(CTX_NW * 64), 0, st, p);
+__global__ __launch_bounds__(CTX_NW * 64) void attn_ctx_rows_kernel(AttnCtxParams p) {
+#define CTX_LIVE_COUNT (p.tk_dev[(long)b])
+#include "attn_ctx_body.h"
+#undef CTX_LIVE_COUNT
+}
+
+template <int D>
+static int launch_attn_ctx(const AttnCtxParams& p, long blocks, bool pre, bool rows, hipStream_t st) {
+    if (rows) hipLaunchKernelGGL((attn_ctx_rows_kernel<D>), dim3((unsigned)blocks), dim3(CTX_NW * 64), 0, st, p);
+    else hipLaunchKernelGGL((attn_ctx_kernel<D>), dim3((unsigned)blocks), dim3(CTX_NW * 64), 0, st, p);
     char tag[64];
-    snprintf(tag, sizeof tag, "attn_ctx_kernel<%d,%s>", D, pre ? "pre" : "scaled");
+    snprintf(tag, sizeof tag, "attn_ctx_kernel<%d,%s%s>", D, pre ? "pre" : "scaled", rows ? ",rows" : "");
     return check_launch(tag);
 }
 
@@ -251,14 +83,11 @@ static int launch_attn_ctx(const AttnCtxParams& p, long blocks, bool pre, hipStr
 
 using namespace mdx;
 
-// Entry for descriptors with tk_dev != NULL; called by the public mdx_attention_* (attention_short.hip) before every other route.
-#if MDX_F16
-extern "C" int mdx_attention_ctx_f16(const MdxAttnDesc* a, void* stream) {
-    const char* op = "mdx_attention_f16";
-#else
-extern "C" int mdx_attention_ctx_bf16(const MdxAttnDesc* a, void* stream) {
-    const char* op = "mdx_attention_bf16";
-#endif
+// Host checks + launch of both forms.  rows = false: tk_dev points to one int32; rows = true: to int32 [B], one count per query batch.
+static int attn_ctx_entry(const MdxAttnDesc* a, void* stream, const char* op, bool rows) {
+    if (rows && !a) return set_error(MDX_EINVAL, "%s: null descriptor", op);
+    if (rows && !a->tk_dev) return set_error(MDX_EINVAL, "%s: tk_dev is NULL: this entry point takes the device address of int32 [B] key counts", op);
+    if (rows && a->kvmap) return set_error(MDX_EINVAL, "%s: tk_dev needs kvmap == NULL (batch b of Q attends to batch b of K / V^T)", op);
     if (a->nsrc != 1) return set_error(MDX_EINVAL, "%s: tk_dev needs nsrc == 1 (nsrc=%ld)", op, (long)a->nsrc);
     if (a->joint != 0) return set_error(MDX_EINVAL, "%s: tk_dev needs joint == 0 (joint=%ld)", op, (long)a->joint);
     if (a->causal != 0) return set_error(MDX_EINVAL, "%s: tk_dev needs causal == 0 (causal=%ld)", op, (long)a->causal);
@@ -292,10 +121,20 @@ extern "C" int mdx_attention_ctx_bf16(const MdxAttnDesc* a, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     const bool pre = a->q_prescaled != 0;
     switch ((int)a->d) {
-        case 16: return launch_attn_ctx<16>(p, blocks, pre, st);
-        case 32: return launch_attn_ctx<32>(p, blocks, pre, st);
-        case 40: return launch_attn_ctx<40>(p, blocks, pre, st);
-        case 80: return launch_attn_ctx<80>(p, blocks, pre, st);
-        default: return launch_attn_ctx<160>(p, blocks, pre, st);
+        case 16: return launch_attn_ctx<16>(p, blocks, pre, rows, st);
+        case 32: return launch_attn_ctx<32>(p, blocks, pre, rows, st);
+        case 40: return launch_attn_ctx<40>(p, blocks, pre, rows, st);
+        case 80: return launch_attn_ctx<80>(p, blocks, pre, rows, st);
+        default: return launch_attn_ctx<160>(p, blocks, pre, rows, st);
     }
 }
+
+// Entry for descriptors with tk_dev != NULL; called by the public mdx_attention_* (attention_short.hip) before every other route.
+// mdx_attention_ctx_rows_*: public (mdx.h), the same descriptor with tk_dev -> int32 [B]; MDX_OP_ATTN_ROWS in a program.
+#if MDX_F16
+extern "C" int mdx_attention_ctx_f16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_f16", false); }
+extern "C" int mdx_attention_ctx_rows_f16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_ctx_rows_f16", true); }
+#else
+extern "C" int mdx_attention_ctx_bf16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_bf16", false); }
+extern "C" int mdx_attention_ctx_rows_bf16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_ctx_rows_bf16", true); }
+#endif

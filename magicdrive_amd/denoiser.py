@@ -93,13 +93,23 @@ class ConditioningBuffers:
     """Input-side device buffers of the conditioning prologue + the ops that turn them into the context tokens
     ehs_with_cam [B, 1+77+L, D] and the per-view map feature (BEVControlNetModel.forward :743-793, 842-850)."""
 
-    def __init__(self, bld: Builder, cn: PackedNet, cfg, n_scene: int, n_cam: int, L_box: int, latent_hw, n_text: int = 77, dynamic: bool = False):
+    def __init__(self, bld: Builder, cn: PackedNet, cfg, n_scene: int, n_cam: int, L_box: int, latent_hw, n_text: int = 77, dynamic=False,
+                 cfg_halves: int = 1):
         """dynamic: L_box is a box CAPACITY.  load() then takes boxes padded to any L <= L_box, fills the first L slots of every view (the
         rest stay masked out: null embeddings, finite) and writes the live context length 1 + n_text + L to `self.live` (int32 [1]), which the
-        context attention reads on the device (ops.Attn.tk_dev)."""
+        context attention reads on the device (ops.Attn.tk_dev).
+        dynamic="scene": one count per view, `self.live` is int32 [B] (ops.Attn.tk_rows): load() writes 1 + n_text + L_scene for every view
+        of a scene, L_scene = the scene's own padded length (1 + the index of its last kept box over its cameras; 0 without one) — what a
+        call of that scene alone would have padded to, so the scene attends to exactly the tokens of its batch-1 call.  cfg_halves = 2: the
+        scenes are [uncond | cond] halves; a scene's count is its cond row's and holds for both halves (the reference pads the uncond boxes
+        to the cond length, add_uncond_to_kwargs)."""
         dev = bld.device
+        assert dynamic in (False, True, "scene"), f"dynamic={dynamic!r}: False, True or 'scene'"
         assert not dynamic or L_box > 0, "a dynamic plan needs a box capacity >= 1"
+        assert cfg_halves in (1, 2) and n_scene % cfg_halves == 0
         self.dynamic = bool(dynamic)
+        self.per_scene = dynamic == "scene"
+        self.cfg_halves = cfg_halves
         H16 = bld.dtype                     # the plan's 16-bit activation type (bf16 or fp16)
         self.dtype = H16
         cc = cfg["controlnet"]; bb = cc["bbox"]
@@ -111,7 +121,8 @@ class ConditioningBuffers:
         self.n_text = n_text
         S = self.S
         self.ctx = torch.zeros(B, S, D, dtype=H16, device=dev)
-        self.live = torch.full((1,), S, dtype=torch.int32, device=dev)      # keys the context attention sees; < S only on a dynamic plan
+        # keys the context attention sees; < S only on a dynamic plan.  One entry, or one per view through the nets (dynamic="scene")
+        self.live = torch.full((B if self.per_scene else 1,), S, dtype=torch.int32, device=dev)
         # camera: [B, 7, 3] fp32 (columns of the (3,7) matrix) -> Fourier 189 -> cam2token -> ctx[:, 0]
         ncol = cc["uncond_cam_in_dim"][1]
         F_cam = cc["cam_embedder_num_freqs"]
@@ -256,7 +267,16 @@ class ConditioningBuffers:
                 self.box_in.view(B, self.L, *bb.shape[3:])[:, :Lb].copy_(bb.reshape(B, Lb, *bb.shape[3:]))
                 self.box_cls.view(B, self.L)[:, :Lb].copy_(cl.to(self.box_cls.device, torch.int64).reshape(B, Lb))
                 self.box_mask.view(B, self.L)[:, :Lb].copy_(mk.to(self.box_mask.device).reshape(B, Lb).to(torch.uint8))
-            if dynamic:                        # an ordinary stream-ordered device write: no host sync, seen by the next replay
+            if dynamic and getattr(self, "per_scene", False):
+                # the scene's own padded length, from the masks, with device ops only (no host sync): for the prefix-form masks of
+                # _preprocess_bbox / collate_samples this is the length a call of the scene alone pads to
+                m = mk.to(self.live.device).reshape(ns, nc * Lb).to(torch.int32)
+                pos = torch.arange(1, Lb + 1, dtype=torch.int32, device=m.device).repeat(nc)
+                Ls = (m * pos).amax(dim=1)                                               # [ns]; 0: no kept box
+                if self.cfg_halves == 2:
+                    Ls = Ls[ns // 2:].repeat(2)
+                self.live.copy_((1 + self.n_text + Ls).view(ns, 1).expand(ns, nc).reshape(-1))
+            elif dynamic:                      # an ordinary stream-ordered device write: no host sync, seen by the next replay
                 self.live.fill_(1 + self.n_text + Lb)
 
 
@@ -278,12 +298,16 @@ class SamplerPlan:
 
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
-                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes: bool = False):
+                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False):
         """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
         1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
-        from cond.live on the device.  Self and cross-view attention are untouched."""
+        from cond.live on the device.  Self and cross-view attention are untouched.
+        dynamic_boxes="scene": the same with one count per view (cond.live is int32 [B], ops.Attn.tk_rows): every scene of a batched call
+        attends to its own boxes only, so its latents equal those of a call of that scene alone up to rounding."""
         self.cfg, self.device = cfg, device
+        assert dynamic_boxes in (False, True, "scene"), f"dynamic_boxes={dynamic_boxes!r}: False, True or 'scene'"
         self.dynamic_boxes = bool(dynamic_boxes)
+        self.scene_boxes = dynamic_boxes == "scene"
         assert not dynamic_boxes or L_box > 0, "dynamic_boxes needs a box capacity >= 1 (calls without boxes keep their exact plan)"
         assert scheduler_kind in ("ddim", "unipc")
         assert given_view_mode in (0, 1, 2)
@@ -315,9 +339,10 @@ class SamplerPlan:
             self.gv_cond = torch.zeros_like(self.x)
             self.gv_noise = torch.zeros_like(self.x)
         # ---------------- prologue ----------------
-        self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text, dynamic=self.dynamic_boxes)
+        self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text, dynamic=dynamic_boxes, cfg_halves=self.c)
         if self.dynamic_boxes:
             bld.ctx_tk_dev = self.cond.live
+            bld.ctx_tk_per_view = self.scene_boxes
         self.temb_cn = TembTable(cn, num_steps, device, per_sample=False)
         self.temb_un = TembTable(unet, num_steps, device, per_sample=False)
         self.temb_cn.sel = self.step_ctr

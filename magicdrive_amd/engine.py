@@ -306,7 +306,9 @@ class Builder:
         self.ops: List[object] = []
         # int32 [1] device tensor or None: when set, every text-context attention (attn2) is emitted with its key count read from it
         # (ops.Attn.tk_dev) and the context K / V^T it is given hold a CAPACITY of keys (denoiser.SamplerPlan dynamic_boxes)
+        # int32 [B] (one count per view through the nets: SamplerPlan dynamic_boxes="scene") is emitted as ops.Attn.tk_rows instead
         self.ctx_tk_dev: Optional[torch.Tensor] = None
+        self.ctx_tk_per_view = False
         self.ws = torch.empty(ws_mb * 1024 * 1024 // 4, dtype=F32, device=device)
         self.groups = cfg["norm_num_groups"]
         self.eps = cfg["norm_eps"]
@@ -514,7 +516,8 @@ class Builder:
         self.pool.put(n2)
         Kc, Vtc, S = ctx_kv[pre + "attn2."]
         ao2 = self.pool.get((B * T, C))
-        self.emit(O.Attn(q2.view(B, T, C), Kc, Vtc, ao2.view(B, T, C), heads=heads, Tk=S, scale=(C // heads) ** -0.5, q_prescaled=True, tk_dev=self.ctx_tk_dev,
+        self.emit(O.Attn(q2.view(B, T, C), Kc, Vtc, ao2.view(B, T, C), heads=heads, Tk=S, scale=(C // heads) ** -0.5, q_prescaled=True,
+                         tk_dev=None if self.ctx_tk_per_view else self.ctx_tk_dev, tk_rows=self.ctx_tk_dev if self.ctx_tk_per_view else None,
                          name=name + ".attn2"))
         self.pool.put(q2)
         has4 = net.has(pre + "attn4.to_q.weight")

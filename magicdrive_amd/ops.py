@@ -259,7 +259,9 @@ class Attn:
     """O = sum_s softmax(Q K_s^T * scale) V_s.  Q [B,Tq,C]; K [Bkv,Tk,C]; Vt [Bkv,C,ldv] (V transposed); O [B,Tq,C].
     v_rowmajor: Vt is V itself, [B,Tk,C] (short sequences only: MdxAttnDesc.v_rowmajor); causal: query t sees keys 0..t.
     tk_dev: int32 [1] on the device — Tk is then the CAPACITY of K / Vt and the kernel attends to the first tk_dev[0] keys, read when
-    it runs (MdxAttnDesc.tk_dev: the context attention of a sampler plan built for a bucket of box counts)."""
+    it runs (MdxAttnDesc.tk_dev: the context attention of a sampler plan built for a bucket of box counts).
+    tk_rows: int32 [B] on the device — the same with one count per query batch: batch b attends to the first tk_rows[b] keys of its own
+    K / Vt (OP_ATTN_ROWS, mdx_attention_ctx_rows_*: the scenes of a batched call attend to their own boxes only)."""
     Q: torch.Tensor
     K: torch.Tensor
     Vt: torch.Tensor
@@ -275,6 +277,7 @@ class Attn:
     causal: bool = False
     v_rowmajor: bool = False
     tk_dev: Optional[torch.Tensor] = None    # int32 [1], same device as Q: the live key count (<= Tk)
+    tk_rows: Optional[torch.Tensor] = None   # int32 [B], same device as Q: the live key count of every query batch; not together with tk_dev
     opcode = L.OP_ATTN
 
     def lower(self):
@@ -310,8 +313,17 @@ class Attn:
             _chk(self.nsrc == 1 and self.kvmap is None and not self.joint and not self.causal and not self.v_rowmajor,
                  f"attn {self.name}: tk_dev serves one source, no joint softmax, no causal mask, the V^T operand")
             d.tk_dev = _p(self.tk_dev)
+        opcode = self.opcode
+        if self.tk_rows is not None:
+            _chk(self.tk_dev is None, f"attn {self.name}: tk_rows and tk_dev are mutually exclusive")
+            _chk(self.tk_rows.dtype == torch.int32 and self.tk_rows.dim() == 1 and self.tk_rows.numel() == B and self.tk_rows.is_contiguous()
+                 and self.tk_rows.device == Q.device, f"attn {self.name}: tk_rows must be int32 [B={B}], contiguous, on the device of Q")
+            _chk(self.nsrc == 1 and self.kvmap is None and not self.joint and not self.causal and not self.v_rowmajor,
+                 f"attn {self.name}: tk_rows serves one source, no joint softmax, no causal mask, the V^T operand")
+            d.tk_dev = _p(self.tk_rows)
+            opcode = L.OP_ATTN_ROWS
         _chk(self.nsrc >= 1 and (self.nsrc <= 8 if self.joint else self.nsrc <= 2), f"attn {self.name}: nsrc={self.nsrc} (joint={self.joint})")
-        return self.opcode, d
+        return opcode, d
 
 
 @dataclass

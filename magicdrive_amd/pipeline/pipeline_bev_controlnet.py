@@ -78,6 +78,13 @@ class StableDiffusionBEVControlNetPipeline:
         # built with SamplerPlan(dynamic_boxes=True) — the context attention reads the live key count from device memory, positions < L_box
         # are computed as on the exact plan and the padded slots up to the capacity are never attended to.  Calls without boxes keep their plan.
         self.box_bucket: Optional[int] = None
+        # Every scene of a batched call attends to its OWN boxes.  The reference pads the boxes of a batch to the batch maximum and its text-context
+        # attention sees the padded slots as null-embedded tokens, so a scene's pictures depend on which scenes share its call; the reference's own
+        # default is one scene per call (validation_batch_size: 1).  False (default): that padded semantics, behaviour and plan key unchanged.
+        # True: a call with boxes uses a plan built with SamplerPlan(dynamic_boxes="scene") at the capacity L_box (ceil(L_box / n) * n under
+        # box_bucket = n); each scene's context length 1 + 77 + L_scene is read per view from device memory, L_scene being the length a call of
+        # that scene alone pads to — its latents then equal the batch-1 call's up to rounding, at any batch size, on one captured plan.
+        self.scene_boxes: bool = False
 
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
@@ -226,15 +233,19 @@ class StableDiffusionBEVControlNetPipeline:
     # ---- the sampler ----
     def _box_plan_geometry(self, L_box: int):
         """(box count the plan is built for, dynamic_boxes, the plan key's box entry) of a call whose boxes are padded to L_box, under
-        self.box_bucket.  The key entry is L_box itself — today's key — unless the plan is dynamic; then (capacity, "dynamic")."""
+        self.box_bucket and self.scene_boxes.  The key entry is L_box itself — today's key — unless the plan is dynamic; then
+        (capacity, "dynamic"), or (capacity, "scene") for per-scene counts."""
         n = self.box_bucket
-        if n is None or L_box <= 0:
+        scene = bool(getattr(self, "scene_boxes", False))
+        if L_box <= 0 or (n is None and not scene):
             return int(L_box), False, int(L_box)
-        if isinstance(n, bool) or int(n) != n or int(n) < 1:
-            raise ValueError(f"box_bucket={n!r}: None or an integer >= 1")
-        n = int(n)
-        cap = -(-int(L_box) // n) * n
-        return cap, True, (cap, "dynamic")
+        cap = int(L_box)
+        if n is not None:
+            if isinstance(n, bool) or int(n) != n or int(n) < 1:
+                raise ValueError(f"box_bucket={n!r}: None or an integer >= 1")
+            n = int(n)
+            cap = -(-int(L_box) // n) * n
+        return (cap, "scene", (cap, "scene")) if scene else (cap, True, (cap, "dynamic"))
 
     def _plan_config(self) -> Dict[str, Any]:
         """Architecture config of the sampler plan: the UNet's, with the conditioning encoders' geometry taken from the ControlNet."""
@@ -265,6 +276,9 @@ class StableDiffusionBEVControlNetPipeline:
             raise NotImplementedError(f"cross_attention_kwargs={cross_attention_kwargs!r}: the fused attention kernels take no processor kwargs")
         if eta != 0.0:
             raise NotImplementedError("the fused samplers are deterministic (DDIM eta = 0, UniPC)")
+        if self.scene_boxes and bbox_max_length is not None:
+            raise ValueError(f"bbox_max_length={bbox_max_length!r} with scene_boxes=True: bbox_max_length asks for the padded slots as tokens every "
+                             "scene attends to, scene_boxes for every scene attending to its own boxes only — pass one of the two")
         if isinstance(self.scheduler, DDIMScheduler):
             sched_kind = "ddim"
         elif isinstance(self.scheduler, UniPCMultistepScheduler):
@@ -356,7 +370,7 @@ class StableDiffusionBEVControlNetPipeline:
             s0, s1 = bounds[ci], bounds[ci + 1]
             # the packed nets' identity and 16-bit type are part of the key: `pipe.unet.to(torch.float16)` re-packs the weights, and a plan
             # built on the old PackedNet would keep running (and keep alive) the old ones
-            # box_bucket: the key carries (capacity, "dynamic") in the place of L_box; None / no boxes: today's key
+            # box_bucket: the key carries (capacity, "dynamic") in the place of L_box, scene_boxes (capacity, "scene"); neither / no boxes: today's key
             key = (s1 - s0, ci, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(controlnet_conditioning_scale), text.shape[1], sched_kind,
                    gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
             plan = self._plans.get(key)

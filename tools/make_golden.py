@@ -51,6 +51,8 @@ weights the HIP model holds — so that the fixture measures arithmetic, not wei
   tiny_forward_rig.pt / tiny_pipeline_rig.pt `... rig`  camera rigs that are not a ring (neighboring_view_pair with one or no neighbour per
                     view): the reference UNet forward on a five-camera open chain and on an asymmetric three-camera rig, and the reference
                     pipeline __call__ on the chain (CFG, 3 boxes, 4 DDIM steps).
+  tiny_pipeline_scene_boxes.pt `... sceneboxes`  the tiny_pipeline.pt recipe (CFG on) on three scenes with 0, 2 and 5 kept boxes, one scene per
+                    reference call: per-scene inputs and output latents (pipe.scene_boxes; tests/scene_boxes_data.py builds the scenes).
   tiny_reference_checks.pt `... refchecks`  parameter shapes of the tiny reference modules; the reference pipeline's refusal of the stock
                     DDIMScheduler (error, message, step() parameters); the reference UniPCMultistepScheduler on a
                     fixed pseudo-model for four (steps, order, solver type) cases — what the oracle tests compare against without the reference.
@@ -362,6 +364,25 @@ def rig_fixture(out_dir, cfg0, usd, csd, meta, hw=(28, 50)):
     print("tiny_pipeline_rig: |x|", x.abs().mean().item(), tuple(x.shape))
 
 
+def scene_boxes_fixture(out_dir, cfg, usd, csd, meta):
+    """tiny_pipeline_scene_boxes.pt: the recipe of tiny_pipeline.pt (reference pipeline __call__, 5 DDIM steps, guidance 2.0 = CFG on) on three
+    scenes with 0, 2 and 5 kept boxes, ONE SCENE PER CALL — the reference's own validation_batch_size: 1, where a scene attends to its own
+    1 + 77 + L_scene context tokens.  What pipe.scene_boxes reproduces inside a batched call (tests/test_scene_boxes*.py)."""
+    import scene_boxes_data as SB
+    ns, pipe = ref_models.build_reference_pipeline(cfg, usd, csd)
+    scenes = SB.make_scenes(cfg)
+    outs = []
+    with torch.no_grad():
+        for sc in scenes:
+            outs.append(pipe(prompt=None, image=sc["bev_map"], camera_param=sc["camera_param"], height=224, width=400, num_inference_steps=SB.STEPS,
+                             guidance_scale=SB.GUIDANCE, latents=sc["latents"].clone(), prompt_embeds=sc["prompt_embeds"],
+                             negative_prompt_embeds=sc["negative_prompt_embeds"], output_type="latent",
+                             bev_controlnet_kwargs={"bboxes_3d_data": sc["bboxes_3d_data"]}).images.clone())
+    torch.save({"meta": meta, "steps": SB.STEPS, "guidance": SB.GUIDANCE, "counts": list(SB.COUNTS), "scenes": [SB.pack_scene(sc) for sc in scenes],
+                "latents": outs}, os.path.join(out_dir, "tiny_pipeline_scene_boxes.pt"))
+    print("tiny_pipeline_scene_boxes: |x|", [o.abs().mean().item() for o in outs], os.path.getsize(os.path.join(out_dir, "tiny_pipeline_scene_boxes.pt")) // 1024, "KiB")
+
+
 def _trace_cb(store, every):
     def cb(i, t, latents):
         if (i + 1) % every == 0:
@@ -563,6 +584,8 @@ def main():
         return zmod_fixture(out_dir, cfg, csd, meta)
     if sys.argv[1:] == ["rig"]:
         return rig_fixture(out_dir, cfg, usd, csd, meta)
+    if sys.argv[1:] == ["sceneboxes"]:
+        return scene_boxes_fixture(out_dir, cfg, usd, csd, meta)
     if sys.argv[1:] in (["res272"], ["res424"]):
         return resolution_fixture(out_dir, cfg, usd, meta, "272x736" if sys.argv[1] == "res272" else "424x800")
 

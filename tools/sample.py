@@ -255,6 +255,9 @@ def main(argv=None):
     ap.add_argument("--cond-on-view", action="store_true", help="demo/run_cond_on_view.py: generation ti is sampled with the encoded ground-truth view ti given")
     ap.add_argument("--box-bucket", type=int, default=None, help="one sampler plan per bucket of N padded box counts (pipe.box_bucket, INTEGRATION.md §1): the "
                     "padded box count changes with almost every batch of a validation run; default: an exact plan per count")
+    ap.add_argument("--scene-boxes", action="store_true", help="every scene of a batch attends to its own boxes only (pipe.scene_boxes, INTEGRATION.md §1): "
+                    "with fix_seed_within_batch=true a scene's pictures are those of the reference's batch-1 run at any --batch-size; default: the "
+                    "reference's padded-batch semantics")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args(argv)
     from magicdrive_amd.dataset import FolderSet
@@ -273,6 +276,8 @@ def main(argv=None):
         if a.box_bucket < 1:
             raise SystemExit("--box-bucket must be >= 1")
         pipe.box_bucket = a.box_bucket
+    if a.scene_boxes:
+        pipe.scene_boxes = True
     data = FolderSet(a.data)
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
