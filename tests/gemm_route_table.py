@@ -53,6 +53,29 @@ def route_lines(c):
     return [(c["name"] + tag, " ".join(f"{k}={v}" for k, v in {**f, **c["opts"]}.items())) for tag, f in sets]
 
 
+def evaluate(lines, workdir):
+    """Build tests/gemm_route_check.cpp with g++ into `workdir`, feed it `lines` ('name key=value ...') and return {name: {field: value}} of what
+    it prints (an error's text under "msg").  None when there is no g++."""
+    import shutil
+    import subprocess
+    gxx = shutil.which("g++")
+    if gxx is None:
+        return None
+    exe = os.path.join(str(workdir), "gemm_route_check")
+    subprocess.run([gxx, "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe, os.path.join(HERE, "gemm_route_check.cpp")], check=True)
+    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    out = {}
+    for line in r.stdout.splitlines():
+        name, rest = line.split(" ", 1)
+        if " msg=" in rest:
+            head, msg = rest.split(" msg=", 1)
+            out[name] = dict(kv.split("=", 1) for kv in head.split()); out[name]["msg"] = msg
+        else:
+            out[name] = dict(kv.split("=", 1) for kv in rest.split())
+    return out
+
+
 def run_case(c):
     """Issue the case to the built library once: (mdx_last_kernel(), SHA-256 of everything it wrote).  Inputs are seeded; the kernels are
     deterministic (split-K slabs, not atomics)."""
