@@ -289,6 +289,19 @@ typedef struct MdxGroupNormDesc {
 } MdxGroupNormDesc;
 int mdx_groupnorm_bf16(const MdxGroupNormDesc* d, void* stream);
 
+/*
+ * mdx_groupnorm_resident_bf16 — the same operation on the same descriptor through ONE kernel that reads the tensor once (additive symbols, the
+ * ABI version stays 12; MDX_OP_GROUPNORM_RESIDENT; mdx_last_kernel() = "gn_resident_kernel").  One workgroup per (image, block of k groups) keeps its
+ * HW x (k * C / G) slab in registers: fp32 mean, then the centred sum of squares from the registers (exact two-pass variance),
+ * normalise (+SiLU), store.  Deterministic; `ws` is not used.  k comes from csrc/gn_route.h (gn_resident_plan).
+ * MDX_EINVAL: every requirement of mdx_groupnorm_bf16 above.
+ * MDX_EUNSUPPORTED, nothing launched and nothing written: option GN_RESIDENT = 0; X or Y not 16-byte aligned, ldx or ldy not a multiple
+ * of 8, fewer than 8 channels per group, no k with k * C / G a multiple of 8 whose slab fits (1024 threads x 24 vectors of 16 bytes,
+ * at most 2560 channels); and, unless GN_RESIDENT = 2, B * HW * C <= GN_ONE_KERNEL_ELEMS.  It never falls back to another kernel, and
+ * mdx_groupnorm_bf16 never routes here.
+ */
+int mdx_groupnorm_resident_bf16(const MdxGroupNormDesc* d, void* stream);
+
 /* mdx_layernorm_bf16 — LayerNorm over the last dim of [M][C] (attention.py:85,104,120; blocks.py:67-71).
  * Requirements (MDX_EINVAL): C, ldx, ldy must be multiples of 8, 0 < C <= ldx, ldy; X, Y, gamma, beta must be 16-byte aligned (rows move as
  * 16-byte pieces, gamma / beta as float4); M fits a 32-bit int.  C > 2048 returns MDX_EUNSUPPORTED. */
@@ -455,6 +468,7 @@ int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream);
 #define MDX_OP_UNIPC 12
 #define MDX_OP_SOFTMAX 13
 #define MDX_OP_ATTN_ROWS 14   /* MdxAttnDesc through mdx_attention_ctx_rows_*: tk_dev -> int32 [B] */
+#define MDX_OP_GROUPNORM_RESIDENT 15   /* MdxGroupNormDesc through mdx_groupnorm_resident_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -476,6 +490,7 @@ int mdx_conv2d_f16(const MdxConvDesc* d, void* stream);
 int mdx_conv2d_direct_f16(const MdxConvDirectDesc* d, void* stream);
 int mdx_attention_f16(const MdxAttnDesc* d, void* stream);
 int mdx_groupnorm_f16(const MdxGroupNormDesc* d, void* stream);
+int mdx_groupnorm_resident_f16(const MdxGroupNormDesc* d, void* stream);
 int mdx_layernorm_f16(const MdxLayerNormDesc* d, void* stream);
 int mdx_elementwise_f16(const MdxEwDesc* d, void* stream);
 int mdx_fourier_embed_f16(const MdxFourierDesc* d, void* stream);

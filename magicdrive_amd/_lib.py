@@ -19,6 +19,7 @@ ABI_VERSION = 12
 OP_GEMM, OP_CONV, OP_CONV_DIRECT, OP_ATTN, OP_GROUPNORM, OP_LAYERNORM = 1, 2, 3, 4, 5, 6
 OP_EW, OP_FOURIER, OP_GATHER, OP_TIMEEMB, OP_DDIM, OP_UNIPC, OP_SOFTMAX = 7, 8, 9, 10, 11, 12, 13
 OP_ATTN_ROWS = 14                     # MdxAttnDesc through mdx_attention_ctx_rows_*: tk_dev -> int32 [B], one key count per query batch
+OP_GROUPNORM_RESIDENT = 15            # MdxGroupNormDesc through mdx_groupnorm_resident_*: the one-read register-resident kernel (csrc/gn_route.h)
 OP_BYTES = 512
 
 EPI_NONE, EPI_GEGLU, EPI_SILU = 0, 1, 2
@@ -68,6 +69,7 @@ ENTRY_OF_OP = {
     OP_FOURIER: "mdx_fourier_embed", OP_GATHER: "mdx_gather_rows", OP_TIMEEMB: "mdx_timestep_embedding", OP_DDIM: "mdx_cfg_ddim_step",
     OP_UNIPC: "mdx_cfg_unipc_step", OP_SOFTMAX: "mdx_softmax_rows",
     OP_ATTN_ROWS: "mdx_attention_ctx_rows_bf16",      # a second entry point of MdxAttnDesc: DESC_OF_OP keeps one op per descriptor type
+    OP_GROUPNORM_RESIDENT: "mdx_groupnorm_resident_bf16",      # likewise of MdxGroupNormDesc
 }
 def entry_name(opcode: int, dtype: int = DTYPE_BF16) -> str:
     """C entry point of an op in the bf16 or the fp16 build (mdx_gemm_bf16 -> mdx_gemm_f16, mdx_elementwise -> mdx_elementwise_f16)."""

@@ -99,6 +99,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
             case MDX_OP_CONV_DIRECT: return mdx_conv2d_direct_f16((const MdxConvDirectDesc*)d, st);
             case MDX_OP_ATTN: return mdx_attention_f16((const MdxAttnDesc*)d, st);
             case MDX_OP_GROUPNORM: return mdx_groupnorm_f16((const MdxGroupNormDesc*)d, st);
+            case MDX_OP_GROUPNORM_RESIDENT: return mdx_groupnorm_resident_f16((const MdxGroupNormDesc*)d, st);
             case MDX_OP_LAYERNORM: return mdx_layernorm_f16((const MdxLayerNormDesc*)d, st);
             case MDX_OP_EW: return mdx_elementwise_f16((const MdxEwDesc*)d, st);
             case MDX_OP_FOURIER: return mdx_fourier_embed_f16((const MdxFourierDesc*)d, st);
@@ -118,6 +119,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
         case MDX_OP_CONV_DIRECT: return mdx_conv2d_direct((const MdxConvDirectDesc*)d, st);
         case MDX_OP_ATTN: return mdx_attention_bf16((const MdxAttnDesc*)d, st);
         case MDX_OP_GROUPNORM: return mdx_groupnorm_bf16((const MdxGroupNormDesc*)d, st);
+        case MDX_OP_GROUPNORM_RESIDENT: return mdx_groupnorm_resident_bf16((const MdxGroupNormDesc*)d, st);
         case MDX_OP_LAYERNORM: return mdx_layernorm_bf16((const MdxLayerNormDesc*)d, st);
         case MDX_OP_EW: return mdx_elementwise((const MdxEwDesc*)d, st);
         case MDX_OP_FOURIER: return mdx_fourier_embed((const MdxFourierDesc*)d, st);

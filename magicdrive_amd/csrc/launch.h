@@ -13,6 +13,7 @@
 #define mdx_conv2d_direct mdx_conv2d_direct_f16
 #define mdx_attention_bf16 mdx_attention_f16
 #define mdx_groupnorm_bf16 mdx_groupnorm_f16
+#define mdx_groupnorm_resident_bf16 mdx_groupnorm_resident_f16
 #define mdx_layernorm_bf16 mdx_layernorm_f16
 #define mdx_elementwise mdx_elementwise_f16
 #define mdx_fourier_embed mdx_fourier_embed_f16

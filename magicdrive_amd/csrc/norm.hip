@@ -631,3 +631,223 @@ extern "C" int mdx_layernorm_bf16(const MdxLayerNormDesc* d, void* stream) {
     p.M = (int)d->M; p.C = (int)d->C; p.ldx = d->ldx; p.ldy = d->ldy; p.eps = (float)d->eps;
     return launch_layernorm<true>(p, (hipStream_t)stream);
 }
+
+#include "gn_route.h"
+
+namespace mdx {
+
+// ------------------------------------------------------------------------------------------------
+// Register-resident GroupNorm (mdx_groupnorm_resident_*, gn_route.h): one workgroup per (image, block of k groups) loads its
+// HW x (k * cpg) slab ONCE, 16 bytes per load, NV vectors per thread, all in flight together; the tensor is read once and written once
+// (the two streaming stages above read it twice).  Thread t owns vector column t % vpr of the pixel rows t / vpr + u * rpp: its 8 channels
+// are the same for every vector it holds, so the per-channel sums live in 8 registers and fall into at most two groups (cpg >= 8):
+// elements [0, split) belong to group glo of the block, the rest to glo + 1.
+// Statistics: fp32 mean first, then the sum of squares of (x - mean) from the same registers — an exact two-pass variance, no pivot.
+// Each statistic takes one reduction through LDS in a fixed order (thread partials -> one wave per group: lanes over the rows, the
+// group's columns in ascending order, then the butterfly of wave_sum), so results are deterministic.  gamma / beta wait in LDS from the
+// start and become scale / shift in place.  No workgroup waits for another.
+// Block order: blocks b, b + 8, ... share an XCD (as in gemm_ws.hip), so the sibling blocks of one image are blockIdx 8 apart — same
+// XCD, next to each other in its dispatch order — and the 128-byte lines two neighbouring row segments share are fetched by one and hit
+// L2 for the other.
+struct GNRParams {
+    const bf16_t* X; bf16_t* Y; const float* gamma; const float* beta;
+    int B, HW, C, G, k, cpg, vpr, rpp; long ldx, ldy; float eps; int silu;
+};
+
+using mdx_route::GNR_THREADS;
+using mdx_route::GNR_MAX_CH;
+using mdx_route::GNR_MAX_K;
+
+// silu_f's 1 / (1 + e^-x) is a full IEEE division (v_div_scale / v_div_fmas / v_div_fixup around v_rcp_f32: ~12 VALU operations per element).
+// One workgroup per CU cannot hide them behind another workgroup's memory phase as the streaming kernels do: v_rcp_f32 itself (1 ulp) here.
+__device__ __forceinline__ float gnr_silu(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+
+template <int NV>
+__global__ __launch_bounds__(GNR_THREADS) void gn_resident_kernel(GNRParams p) {
+    __shared__ float part[2][GNR_THREADS];                       // per thread: its share of group glo / of group glo + 1
+    __shared__ float gst[2][GNR_MAX_K];                          // per group of the block: sum -> mean, centred sum of squares
+    __shared__ __attribute__((aligned(16))) float lsc[GNR_MAX_CH], lsh[GNR_MAX_CH];      // gamma / beta, then scale / shift
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nb = p.G / p.k;                                    // blocks per image
+    const int xcd = blockIdx.x & 7, kq = blockIdx.x >> 3;
+    const int sib = kq % nb, b = (kq / nb) * 8 + xcd;
+    if (b >= p.B) return;                                        // the grid is padded to 8 images per round (whole workgroups leave)
+    const int cpg = p.cpg, vpr = p.vpr, rpp = p.rpp, HW = p.HW, kc = p.k * cpg;
+    const int ch0 = sib * kc;
+    int rl = tid / vpr, col = tid - rl * vpr;
+    const bool live = rl < rpp;
+    if (!live) { rl = 0; col = 0; }                              // threads past rpp * vpr shadow thread 0: valid loads, partials nobody reads, no stores
+    const int glo = (col * 8) / cpg;
+    const int split = min(8, (glo + 1) * cpg - col * 8);
+    const int ldx = (int)p.ldx, ldy = (int)p.ldy;
+    const bf16_t* xb = p.X + (long)b * HW * p.ldx + ch0 + col * 8;
+    bf16_t* yb = p.Y + (long)b * HW * p.ldy + ch0 + col * 8;
+
+    // every load unconditional from a clamped row (a guarded load becomes a branch with a full wait inside), masked on use.  The launcher
+    // picks the smallest NV >= ceil(HW / rpp) of steps of 4 (the last: 2), so only the last 4 vectors of a thread can lie past the image: the
+    // others carry no mask (a mask per vector is an SGPR pair each, spilled from NV = 20 on)
+    constexpr int UM = NV - 4;                                   // first vector index that needs its mask
+    const int cg = tid < kc ? tid : 0;                           // gamma / beta first: their wait then leaves the slab's loads in flight
+    const float gam = p.gamma[ch0 + cg], bet = p.beta[ch0 + cg];
+    uint4 d[NV];
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int px = rl + u * rpp;
+        d[u] = *(const uint4*)(xb + (u < UM || px < HW ? px : HW - 1) * ldx);
+    }
+    // the slab stays PACKED, NV x 4 registers, from here to the stores: without these fences the compiler keeps the unpacked values of one pass
+    // alive for the next (twice the registers, spilled to scratch from NV = 12 on) and, in the fp16 build, splits the loads into halves
+    auto keep_packed = [&]() {
+#pragma unroll
+        for (int u = 0; u < NV; ++u) asm volatile("" : "+v"(d[u].x), "+v"(d[u].y), "+v"(d[u].z), "+v"(d[u].w));
+    };
+    keep_packed();
+    float okf[4];                                                // 1 / 0: is vector UM + i inside the image?  A vector outside is zeroed once, here
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int u = UM + i;
+        const bool ok = rl + u * rpp < HW;
+        okf[i] = ok ? 1.f : 0.f;
+        d[u].x = ok ? d[u].x : 0u; d[u].y = ok ? d[u].y : 0u; d[u].z = ok ? d[u].z : 0u; d[u].w = ok ? d[u].w : 0u;
+    }
+    if (tid < kc) { lsc[tid] = gam; lsh[tid] = bet; }            // kc <= GNR_MAX_CH = GNR_THREADS
+
+    const float inv_n = 1.0f / ((float)HW * (float)cpg);
+    // one statistic: thread partials -> part, one wave per group adds them up in a fixed order -> gst[which]
+    auto reduce = [&](const float* s, int which) {
+        float lo = 0.f, hi = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { if (e < split) lo += s[e]; else hi += s[e]; }
+        part[0][tid] = lo; part[1][tid] = hi;
+        __syncthreads();
+        for (int g = wave; g < p.k; g += GNR_THREADS / 64) {
+            const int c0 = (g * cpg) / 8, c1 = ((g + 1) * cpg - 1) / 8;
+            float acc = 0.f;
+            for (int r = lane; r < rpp; r += 64)
+                for (int c = c0; c <= c1; ++c) acc += part[(c * 8) / cpg == g ? 0 : 1][r * vpr + c];      // a column that starts in g - 1 gives its upper part
+            acc = wave_sum(acc);
+            if (lane == 0) gst[which][g] = acc;
+        }
+        __syncthreads();
+    };
+
+    float s[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+    __builtin_amdgcn_sched_barrier(0);                           // (nothing of the passes' unpacking moves up here either: fp16 build)
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        Frag8 f; f.u = d[u];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] += bf2f(f.h[e]);
+        __builtin_amdgcn_sched_barrier(0);                       // one vector at a time: interleaved, the unpacked vectors of several iterations
+    }                                                            // push the 22-vector form past its 128 registers
+    reduce(s, 0);
+    keep_packed();
+    const int ghi = glo + 1 < p.k ? glo + 1 : glo;
+    const float mlo = gst[0][glo] * inv_n, mhi = gst[0][ghi] * inv_n;
+    float mp[4];                                                 // mean per channel PAIR: cpg is even (gn_route.h), so is split
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { mp[q] = 2 * q < split ? mlo : mhi; asm volatile("" : "+v"(mp[q])); }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] = 0.f;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        Frag8 f; f.u = d[u];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float dl = bf2f(f.h[e]) - mp[e >> 1];
+            if (u >= UM) dl *= okf[u - UM < 0 ? 0 : u - UM];
+            s[e] = __builtin_fmaf(dl, dl, s[e]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    reduce(s, 1);
+    keep_packed();
+    if (tid < kc) {                                              // same thread, same slot as the gamma / beta fill
+        const int g = tid / cpg;
+        const float sc = rsqrtf(gst[1][g] * inv_n + p.eps) * lsc[tid];
+        lsc[tid] = sc; lsh[tid] = lsh[tid] - gst[0][g] * inv_n * sc;
+    }
+    __syncthreads();
+    if (!live) return;
+    int rls = rl;                                                // the store offsets are worked out here, not beside the loads' (and carried across the passes)
+    asm volatile("" : "+v"(rls));
+    // scale / shift of the thread's 8 channels: in 16 registers, or (LEAN, the slabs of more than 16 vectors per thread, which leave no room
+    // for them) read from LDS four channels at a time for every vector — 64 bytes of LDS per 16 stored, far below the LDS rate
+    constexpr bool LEAN = NV > 16;
+    float4 a[2], h[2];
+    if constexpr (!LEAN) {
+        a[0] = *(const float4*)(lsc + col * 8); a[1] = *(const float4*)(lsc + col * 8 + 4);
+        h[0] = *(const float4*)(lsh + col * 8); h[1] = *(const float4*)(lsh + col * 8 + 4);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < NV; ++u) {
+        const int px = rls + u * rpp;
+        Frag8 f; f.u = d[u];
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            float4 sc, sh;
+            if constexpr (LEAN) {
+                asm volatile("" ::: "memory");                   // keeps the reads of every vector where they are (not hoisted into 16 registers)
+                sc = *(const float4*)(lsc + col * 8 + q * 4); sh = *(const float4*)(lsh + col * 8 + q * 4);
+            } else {
+                sc = a[q]; sh = h[q];
+            }
+            float y0 = __builtin_fmaf(bf2f(f.h[q * 4 + 0]), sc.x, sh.x), y1 = __builtin_fmaf(bf2f(f.h[q * 4 + 1]), sc.y, sh.y);
+            float y2 = __builtin_fmaf(bf2f(f.h[q * 4 + 2]), sc.z, sh.z), y3 = __builtin_fmaf(bf2f(f.h[q * 4 + 3]), sc.w, sh.w);
+            if (p.silu) { y0 = gnr_silu(y0); y1 = gnr_silu(y1); y2 = gnr_silu(y2); y3 = gnr_silu(y3); }
+            w[q * 2] = pack2bf(y0, y1); w[q * 2 + 1] = pack2bf(y2, y3);
+        }
+        if (u < UM || px < HW) *(uint4*)(yb + px * ldy) = make_uint4(w[0], w[1], w[2], w[3]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// descriptor checks of mdx_groupnorm_resident_* (those of mdx_groupnorm_*)
+static int gn_resident_check(const char* op, const MdxGroupNormDesc* d) {
+    if (!d || !d->X || !d->Y || !d->gamma || !d->beta) return set_error(MDX_EINVAL, "%s: null operand", op);
+    if (d->G <= 0 || d->C % d->G) return set_error(MDX_EINVAL, "groupnorm: C=%ld not divisible by G=%ld", (long)d->C, (long)d->G);
+    MDX_NEED(need_int(op, "B", d->B)); MDX_NEED(need_int(op, "HW", d->HW)); MDX_NEED(need_int(op, "C", d->C)); MDX_NEED(need_int(op, "G", d->G));
+    MDX_NEED(need_aligned(op, "gamma", d->gamma, 16)); MDX_NEED(need_aligned(op, "beta", d->beta, 16)); MDX_NEED(need_aligned(op, "ws", d->ws, 16));
+    MDX_NEED(need_aligned(op, "X", d->X, 2)); MDX_NEED(need_aligned(op, "Y", d->Y, 2));
+    if (d->C <= 0 || d->ldx < d->C || d->ldy < d->C) return set_error(MDX_EINVAL, "%s: need 0 < C <= ldx, ldy", op);
+    return MDX_OK;
+}
+
+}  // namespace mdx
+
+// The register-resident route as an op of its own (MDX_OP_GROUPNORM_RESIDENT): same descriptor, same checks, ONE kernel or
+// MDX_EUNSUPPORTED — never another route (mdx_groupnorm_* above routes exactly as before and never comes here).
+extern "C" int mdx_groupnorm_resident_bf16(const MdxGroupNormDesc* d, void* stream) {
+    const char* op = "mdx_groupnorm_resident_bf16";
+    if (int rc = gn_resident_check(op, d)) return rc;
+    if (d->B <= 0 || d->HW <= 0) return MDX_OK;
+    const long mode = opt(OPT_GN_RESIDENT);
+    if (mode <= 0) return set_error(MDX_EUNSUPPORTED, "%s: switched off (option GN_RESIDENT = 0)", op);
+    const long align = (((uintptr_t)d->X | (uintptr_t)d->Y) & 15) == 0 ? 16 : 1;
+    int k = mdx_route::gn_resident_plan(d->B, d->HW, d->C, d->G, d->ldx, d->ldy, align, mode >= 2 ? 0 : opt(OPT_GN_ONE_KERNEL_ELEMS));
+    const long force_k = opt(OPT_GN_RESIDENT_K);
+    if (k && force_k > 0) k = mdx_route::gn_resident_nv(d->HW, d->C, d->G, force_k) ? (int)force_k : 0;
+    if (!k)
+        return set_error(MDX_EUNSUPPORTED, "%s: [%ld][%ld][%ld] G=%ld ldx=%ld ldy=%ld is not served (gn_route.h: slab, 16-byte rows, size rule)", op,
+                         (long)d->B, (long)d->HW, (long)d->C, (long)d->G, (long)d->ldx, (long)d->ldy);
+    GNRParams p;
+    p.X = (const bf16_t*)d->X; p.Y = (bf16_t*)d->Y; p.gamma = d->gamma; p.beta = d->beta;
+    p.B = (int)d->B; p.HW = (int)d->HW; p.C = (int)d->C; p.G = (int)d->G; p.ldx = d->ldx; p.ldy = d->ldy;
+    p.eps = (float)d->eps; p.silu = (int)d->silu;
+    p.k = k; p.cpg = p.C / p.G; p.vpr = k * p.cpg / 8; p.rpp = GNR_THREADS / p.vpr;
+    const int nv = mdx_route::gn_resident_nv(p.HW, p.C, p.G, k);
+    const dim3 grid((unsigned)(((p.B + 7) / 8) * 8 * (p.G / k))), block(GNR_THREADS);
+    hipStream_t st = (hipStream_t)stream;
+    if (nv <= 4) hipLaunchKernelGGL(gn_resident_kernel<4>, grid, block, 0, st, p);
+    else if (nv <= 8) hipLaunchKernelGGL(gn_resident_kernel<8>, grid, block, 0, st, p);
+    else if (nv <= 12) hipLaunchKernelGGL(gn_resident_kernel<12>, grid, block, 0, st, p);
+    else if (nv <= 16) hipLaunchKernelGGL(gn_resident_kernel<16>, grid, block, 0, st, p);
+    else if (nv <= 20) hipLaunchKernelGGL(gn_resident_kernel<20>, grid, block, 0, st, p);
+    else hipLaunchKernelGGL(gn_resident_kernel<mdx_route::GNR_MAX_NV>, grid, block, 0, st, p);
+    return check_launch("gn_resident_kernel");
+}

@@ -51,6 +51,8 @@ namespace mdx {
     X(GN_FINALIZE_CHUNKS, 16, "two-stage GroupNorm: with more chunks per image than this the chunk partials are combined once by gn_finalize_kernel (0 = always in the apply pass)") \
     X(GN_ONE_KERNEL_ELEMS, (4L << 20), "GroupNorm tensors of at most this many elements (all images) take the one-launch kernel (one workgroup per (image, group)) instead of the two streaming passes") \
     X(GN_TWO_STAGE, 1, "streaming two-stage GroupNorm for maps >= 32768 elements") \
+    X(GN_RESIDENT, 1, "register-resident one-read GroupNorm (gn_resident_kernel, an op of its own: MDX_OP_GROUPNORM_RESIDENT): 0 off (the engine emits none, the entry point refuses), 1 where gn_route.h says so (tensors above GN_ONE_KERNEL_ELEMS), 2 whenever the kernel can serve the shape") \
+    X(GN_RESIDENT_K, 0, "force the groups per workgroup of gn_resident_kernel (0 = gn_route.h: the widest block that fits; tools/gn_bench.py sweeps it)") \
     X(XL_PERSIST, 1, "256x256 XL GEMMs (plain / GEGLU, optional residual) on the persistent kernel gemm_xlp_kernel") \
     X(XD, 0, "W-direct persistent GEMM (gemm_xd.hip: weights global -> registers, finished tile stored under the next tile's main loop) for the 256x256 XL GEMMs whose descriptor carries Wq (K % 128 == 0, K >= 640); bit-identical to gemm_xlp_kernel, measured 0.89-1.04x of it (profiles/r06_xd_ab.log): off by default") \
     X(XL_RASTER, 2, "XL tile order: 0 row-major, 1 XCD-strided M-tiles, 2 XCD-blocked (M-group x N-group panels per XCD)") \

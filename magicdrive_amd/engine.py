@@ -22,6 +22,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import _lib as L
+from . import gn_route as GR
 from . import ops as O
 from . import packing as PK
 from .networks.spec import heads_at
@@ -296,6 +297,8 @@ class Builder:
 
     fold_upsample = None                  # Upsample2D as one upsampled-2x conv: None = on GPU devices, True / False = forced (upsample_conv_folds)
 
+    gn_resident = None                    # GroupNorm as the one-read resident op: None = option GN_RESIDENT on GPU devices, 0 / 1 / 2 = that mode forced (tests)
+
     def __init__(self, cfg, device, n_views: int, n_cam: int, ws_mb: int = 64, dtype=BF16):
         self.cfg = cfg
         self.device = device
@@ -370,7 +373,19 @@ class Builder:
 
     def groupnorm(self, net, pre, x: Act, eps, silu, name) -> Act:
         y = self.new(x.B, x.H, x.W, x.C)
-        self.emit(O.GroupNorm(x.btc, y.btc, net.vec(pre + "weight"), net.vec(pre + "bias"), self.groups, eps, silu, ws=self.ws, name=name))
+        xv, yv = x.btc, y.btc
+        # the one-read register-resident kernel where csrc/gn_route.h takes the tensor (option GN_RESIDENT, GPU plans only: a plan built on
+        # the CPU keeps the op the interpreter of the tests and every recorded program know)
+        kind = O.GroupNorm
+        mode, floor = self.gn_resident, GR.GNR_ONE_KERNEL_ELEMS
+        if mode is None:
+            mode = L.get_option("GN_RESIDENT") if torch.device(self.device).type == "cuda" else 0
+            floor = L.get_option("GN_ONE_KERNEL_ELEMS") if mode > 0 else floor
+        if mode > 0:
+            align = 16 if (xv.data_ptr() | yv.data_ptr()) % 16 == 0 else 1
+            if GR.gn_resident_plan(x.B, x.H * x.W, x.C, self.groups, xv.stride(1), yv.stride(1), align, 0 if mode >= 2 else floor):
+                kind = O.GroupNormResident
+        self.emit(kind(xv, yv, net.vec(pre + "weight"), net.vec(pre + "bias"), self.groups, eps, silu, ws=self.ws, name=name))
         return y
 
     def layernorm(self, net, pre, x: torch.Tensor, name) -> torch.Tensor:

@@ -354,6 +354,13 @@ class GroupNorm:
 
 
 @dataclass
+class GroupNormResident(GroupNorm):
+    """The same operation through mdx_groupnorm_resident_*: ONE kernel that reads the tensor once (csrc/gn_route.h says which shapes it
+    takes; the library returns MDX_EUNSUPPORTED for the others and never falls back).  Same fields, same descriptor."""
+    opcode = L.OP_GROUPNORM_RESIDENT
+
+
+@dataclass
 class LayerNorm:
     X: torch.Tensor      # [M, C]
     Y: torch.Tensor
