@@ -453,6 +453,36 @@ typedef struct MdxUniPCDesc {
 } MdxUniPCDesc;
 int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream);
 
+/*
+ * mdx_group_stats_bf16 / _f16 — per-group sample-health record of a tensor: one pass, no atomics, no host sync (additive symbols, the ABI
+ * version stays 12; MDX_OP_GROUP_STATS; csrc/stats.hip).  The library's other error signal is a NaN written into a result (mdx_cfg_ddim_step
+ * at a step index of -1, MdxAttnDesc.tk_dev out of range); this op is how a caller that never looks at the values themselves — a sampling
+ * driver that hands latents to the VAE and the VAE's output to a PNG encoder — gets to see it, per view, without leaving the stream.
+ *   X   : G groups of n contiguous elements, group g at X + g * sG (element strides).  f32 == 1: fp32 (the latents of a sampler plan,
+ *         fp32 NHWC [views][h][w][4]: one group = one view) in either build; f32 == 0: the 16-bit type of the build (decoded images,
+ *         activations).
+ *   out : fp32 [n_rows][G][4], record of group g = {nonfinite, absmax, sum, sumsq}:
+ *           nonfinite  count of NaN / +-Inf elements (fp32, exact: n <= 2^24), recognised by their exponent bits, not by comparisons;
+ *           absmax     largest magnitude over the FINITE elements, 0 without one (bit-exact);
+ *           sum, sumsq over the finite elements, fp32 accumulation in a fixed order: one workgroup per group, per-thread strided
+ *                      16-byte pieces, wave-64 butterfly, fixed-order combine of the waves through LDS — the bits of a record depend on
+ *                      the group's own n elements only (not on G or on the other groups); the longest addition chain is
+ *                      k(n) = ceil(ceil(n / V) / 256) + log2(V) + 9 with V = 4 (fp32) or 8 (16-bit) elements per piece.
+ *   row_dev : NULL, or a device pointer to ONE int32 (4-byte aligned), e.g. a plan's step counter.  The records of a launch go to row
+ *         *row_dev of `out`, read on the device when the kernel RUNS (a replayed hipGraph sees the value current at replay, like
+ *         MdxDdimDesc.step_ptr); a row outside [0, n_rows) writes NOTHING.  NULL: row 0, n_rows is ignored.
+ * The 16-byte loads are taken when X is 16-byte aligned and (G == 1 or sG * element size is a multiple of 16); any other alignment is
+ * SERVED by scalar loads in the same summation order (same bits).  Nothing is read outside [X + g * sG, X + g * sG + n).
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): X and out not NULL; f32 in {0, 1}; 0 <= n <= 2^24; 0 <= G fits a 32-bit int;
+ * sG >= 0; X at its element's natural alignment (4 / 2 bytes); out 16-byte aligned (a record is one 16-byte store); with row_dev: row_dev
+ * 4-byte aligned, 1 <= n_rows fits a 32-bit int.  G == 0 or n == 0: MDX_OK, nothing is launched and nothing written.
+ */
+typedef struct MdxStatsDesc {
+    const void* X; float* out; const int32_t* row_dev;
+    int64_t G, n, sG, n_rows, f32;
+} MdxStatsDesc;
+int mdx_group_stats_bf16(const MdxStatsDesc* d, void* stream);
+
 /* ---- program = array of ops, executed in order on one stream ------------ */
 #define MDX_OP_GEMM 1
 #define MDX_OP_CONV 2
@@ -469,6 +499,7 @@ int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream);
 #define MDX_OP_SOFTMAX 13
 #define MDX_OP_ATTN_ROWS 14   /* MdxAttnDesc through mdx_attention_ctx_rows_*: tk_dev -> int32 [B] */
 #define MDX_OP_GROUPNORM_RESIDENT 15   /* MdxGroupNormDesc through mdx_groupnorm_resident_* */
+#define MDX_OP_GROUP_STATS 16          /* MdxStatsDesc through mdx_group_stats_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -500,6 +531,7 @@ int mdx_cfg_ddim_step_f16(const MdxDdimDesc* d, void* stream);
 int mdx_cfg_unipc_step_f16(const MdxUniPCDesc* d, void* stream);
 int mdx_softmax_rows_f16(const MdxSoftmaxDesc* d, void* stream);
 int mdx_attention_ctx_rows_f16(const MdxAttnDesc* d, void* stream);
+int mdx_group_stats_f16(const MdxStatsDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -109,6 +109,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
             case MDX_OP_UNIPC: return mdx_cfg_unipc_step_f16((const MdxUniPCDesc*)d, st);
             case MDX_OP_SOFTMAX: return mdx_softmax_rows_f16((const MdxSoftmaxDesc*)d, st);
             case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_f16((const MdxAttnDesc*)d, st);
+            case MDX_OP_GROUP_STATS: return mdx_group_stats_f16((const MdxStatsDesc*)d, st);
             default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
         }
     }
@@ -129,6 +130,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
         case MDX_OP_UNIPC: return mdx_cfg_unipc_step((const MdxUniPCDesc*)d, st);
         case MDX_OP_SOFTMAX: return mdx_softmax_rows((const MdxSoftmaxDesc*)d, st);
         case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_bf16((const MdxAttnDesc*)d, st);
+        case MDX_OP_GROUP_STATS: return mdx_group_stats_bf16((const MdxStatsDesc*)d, st);
         default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
     }
 }

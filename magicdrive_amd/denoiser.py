@@ -298,13 +298,20 @@ class SamplerPlan:
 
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
-                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False):
+                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None):
         """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
         1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
         from cond.live on the device.  Self and cross-view attention are untouched.
         dynamic_boxes="scene": the same with one count per view (cond.live is int32 [B], ops.Attn.tk_rows): every scene of a batched call
-        attends to its own boxes only, so its latents equal those of a call of that scene alone up to rounding."""
+        attends to its own boxes only, so its latents equal those of a call of that scene alone up to rounding.
+        health: per-view sample-health records of the latents (ops.GroupStats over self.x: one group per view; health_table()).
+          None (default): nothing is emitted — prologue and step programs are op for op those of a plan built without the argument.
+          "trace": ONE op appended to the step program, behind the scheduler step, row-selected by step_ctr: one record per step and view,
+                   written inside the captured step graph (at which step did a view die?).
+          "final": no per-step op; run_health() launches one op over the final latents behind the loop."""
         self.cfg, self.device = cfg, device
+        assert health in (None, "final", "trace"), f"health={health!r}: None, 'final' or 'trace'"
+        self.health = health
         assert dynamic_boxes in (False, True, "scene"), f"dynamic_boxes={dynamic_boxes!r}: False, True or 'scene'"
         self.dynamic_boxes = bool(dynamic_boxes)
         self.scene_boxes = dynamic_boxes == "scene"
@@ -410,8 +417,19 @@ class SamplerPlan:
                           gv_last_step=num_steps - 1)
             bld.emit(O.UniPCStep(self.x.view(-1), self.eps.view(-1), self.coef, self.step_ctr, self.x_last.view(-1), self.m1.view(-1),
                                  self.m2.view(-1), x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, guidance=guidance_scale, xin_c=Cl, name="cfg+unipc", **gv))
+        self._health = None
+        self.health_ops: List = []
+        if health == "trace":
+            # the scheduler op has already advanced step_ctr when this op runs: step s selects row s + 1 of the storage.  Row 0 is a pad no
+            # step selects, and a replay past the last step selects a row outside the storage (nothing is written).
+            self._health = torch.zeros(num_steps + 1, b * n_cam, 4, dtype=F32, device=device)
+            bld.emit(O.GroupStats(self.x.view(b * n_cam, -1), self._health, row=self.step_ctr, name="health.trace"))
+        elif health == "final":
+            self._health = torch.zeros(1, b * n_cam, 4, dtype=F32, device=device)
+            self.health_ops = [O.GroupStats(self.x.view(b * n_cam, -1), self._health, name="health.final")]
         self.step_ops = bld.ops
         bld.ops = []
+        self.health_prog: Optional[L.Program] = None
         self.prologue: Optional[L.Program] = None
         self.step: Optional[L.Program] = None
         self.step_cn = self.step_enc = self.step_tail = None    # fork: the three parts of the step as programs of their own
@@ -419,6 +437,8 @@ class SamplerPlan:
 
     def compile(self):
         self.prologue = O.build_program(self.prologue_ops)
+        if self.health_ops:
+            self.health_prog = O.build_program(self.health_ops)
         if self.fork_at is None:
             self.step = O.build_program(self.step_ops)
         else:
@@ -448,6 +468,21 @@ class SamplerPlan:
         main.wait_event(done)
         go(self.step_tail, main)
 
+    def health_table(self) -> Optional[torch.Tensor]:
+        """The plan's health records on the device, fp32 {nonfinite, absmax, sum, sumsq} per view (view = scene * n_cam + cam):
+        "trace": [num_steps, b * n_cam, 4], row s written by step s (rows of steps that have not run yet are zero);
+        "final": [1, b * n_cam, 4], written by run_health().  None with health off.  Zeroed by load_inputs."""
+        if self._health is None:
+            return None
+        return self._health[1:] if self.health == "trace" else self._health
+
+    def run_health(self, stream: int) -> None:
+        """health="final": the one record launch over the final latents, on `stream` (raw hipStream_t), behind the last step.  Else nothing."""
+        if self.health_ops:
+            if self.health_prog is None:
+                self.health_prog = O.build_program(self.health_ops)
+            self.health_prog.run(stream)
+
     def release(self):
         """Drop the captured graph and every device buffer this plan owns (called on LRU eviction).  The plan's last replay may still
         be in flight (an output_type='latent' caller that has not synchronised): destroying a hipGraphExec / freeing its buffers under
@@ -459,6 +494,7 @@ class SamplerPlan:
                 prog.destroy()
         self.prologue = self.step = self.step_cn = self.step_enc = self.step_tail = None
         self.prologue_ops = self.step_ops = []
+        self.health_ops, self.health_prog = [], None
         self.bld = None
         self.cond = self.temb_cn = self.temb_un = self.kv_cn = self.kv_un = None
 
@@ -492,6 +528,8 @@ class SamplerPlan:
         self.temb_cn.t.copy_(t); self.temb_un.t.copy_(t)
         self.coef.copy_(coef.to(self.device, F32))
         self.step_ctr.zero_()
+        if self._health is not None:
+            self._health.zero_()
         if self.scheduler_kind == "unipc":
             self.x_last.zero_(); self.m1.zero_(); self.m2.zero_()
 
@@ -508,6 +546,7 @@ class SamplerPlan:
                 self.step.launch(st)
             else:
                 self.step.run(st)
+        self.run_health(st)
         return self.latents()
 
     def latents(self) -> torch.Tensor:

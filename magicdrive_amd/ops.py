@@ -632,6 +632,43 @@ class UniPCStep:
         return self.opcode, d
 
 
+@dataclass
+class GroupStats:
+    """Sample-health records (MdxStatsDesc, csrc/stats.hip): out[row, g] = {nonfinite, absmax, sum, sumsq} of X[g], fp32.
+    X [G, ...]: fp32 or 16-bit, every X[g] dense (group stride X.stride(0)); out fp32 [G, 4], or [n_rows, G, 4] with `row`
+    (int32 [1] on the device, read when the kernel runs: a plan's step counter); a row outside the table writes nothing."""
+    X: torch.Tensor
+    out: torch.Tensor
+    row: Optional[torch.Tensor] = None
+    name: str = ""
+    opcode = L.OP_GROUP_STATS
+
+    @staticmethod
+    def chain_length(n: int, f32: bool) -> int:
+        """k(n) of csrc/stats.hip's head comment: the longest chain of fp32 additions between an element and the stored sum / sumsq —
+        a thread's own pieces, the tree over its V accumulators, the tail element, 6 butterfly levels, 2 levels over the 4 waves."""
+        V = 4 if f32 else 8
+        return -(-(-(-n // V)) // 256) + (2 if f32 else 3) + 1 + 6 + 2
+
+    def lower(self):
+        X, out = self.X, self.out
+        _chk(X.dim() >= 1 and X.dtype in (F32,) + H16, f"stats {self.name}: X must be fp32 or 16-bit [G, ...]")
+        G = X.shape[0]
+        n = X.numel() // G if G else 0
+        _chk(G == 0 or X[0].is_contiguous(), f"stats {self.name}: every group must be dense, got shape {tuple(X.shape)} stride {X.stride()}")
+        _chk(out.dtype == F32 and out.is_contiguous() and out.dim() in (2, 3) and tuple(out.shape[-2:]) == (G, 4), f"stats {self.name}: out must be fp32 [rows, G={G}, 4]")
+        d = L.MdxStatsDesc()
+        d.X, d.out = _p(X), _p(out)
+        d.G, d.n, d.sG, d.f32 = G, n, (X.stride(0) if G > 1 else n), int(X.dtype == F32)
+        d.n_rows = out.shape[0] if out.dim() == 3 else 1
+        if self.row is not None:
+            _chk(self.row.dtype == torch.int32 and self.row.numel() == 1 and self.row.device == X.device, f"stats {self.name}: row must be one int32 on the device of X")
+            d.row_dev = _p(self.row)
+        else:
+            _chk(out.dim() == 2 or out.shape[0] == 1, f"stats {self.name}: a table of rows needs `row`")
+        return self.opcode, d
+
+
 def dtype_code(op) -> int:
     """MdxOp.dtype of an IR op: fp16 when its 16-bit tensors are torch.float16, else bf16 (ops without 16-bit tensors run either build)."""
     for v in vars(op).values():

@@ -29,9 +29,36 @@ from ..schedulers import DDIMScheduler, UniPCMultistepScheduler
 
 
 @dataclass
+class SampleHealth:
+    """Per-scene health of one pipeline call (`pipe.health`), from the device-side records of ops.GroupStats (csrc/stats.hip).
+    A record is fp32 {nonfinite, absmax, sum, sumsq} of one view's latents.  Scene indices are those of the call (global over its chunks)."""
+    ok: List[bool]                                  # [B]: no bad record (and no non-finite decoded pixel)
+    first_bad_step: Optional[List[int]]             # [B], "trace" only: first step whose record is bad, -1 if none (a scene bad only in its pixels keeps -1)
+    final: np.ndarray                               # [B, n_cam, 4]: records of the final latents
+    trace: Optional[np.ndarray] = None              # [n_steps, B, n_cam, 4], "trace" only
+    image_nonfinite: Optional[np.ndarray] = None    # [B, n_cam]: non-finite values of each decoded view; None for output_type="latent"
+
+    @property
+    def bad_scenes(self) -> List[int]:
+        return [i for i, ok in enumerate(self.ok) if not ok]
+
+
+class SampleHealthError(RuntimeError):
+    """pipe.health_action = "raise": some scenes of the call are bad.  `.bad_scenes` names them, `.health` holds the records and `.output`
+    what the call would have returned."""
+
+    def __init__(self, bad_scenes, health=None, output=None):
+        self.bad_scenes = list(bad_scenes)
+        self.health = health
+        self.output = output
+        super().__init__(f"bad samples: scenes {self.bad_scenes} (non-finite or out-of-range latents / pixels)")
+
+
+@dataclass
 class BEVStableDiffusionPipelineOutput:
     images: Union[List[List[Any]], np.ndarray, torch.Tensor]
     nsfw_content_detected: Optional[List[bool]]
+    health: Optional[SampleHealth] = None           # pipe.health is None: None
 
 
 class _NullBar:
@@ -85,6 +112,16 @@ class StableDiffusionBEVControlNetPipeline:
         # box_bucket = n); each scene's context length 1 + 77 + L_scene is read per view from device memory, L_scene being the length a call of
         # that scene alone pads to — its latents then equal the batch-1 call's up to rounding, at any batch size, on one captured plan.
         self.scene_boxes: bool = False
+        # Per-scene sample health.  The library reports what it cannot report without a host sync by writing NaN into the result, and this
+        # pipeline hands latents to the VAE and pixels to a uint8 cast: a scene whose latents went non-finite (or blew up) becomes pictures
+        # with no error anywhere.  None (default): nothing is emitted or copied, plan keys unchanged.  "final": one record launch per chunk
+        # over the final latents.  "trace": one record per step and view from inside the captured step graphs (first_bad_step).  Either way
+        # the records reach the host in ONE copy at the end of the call (no sync inside the loop) as output.health (SampleHealth).
+        self.health: Optional[str] = None
+        self.health_action: str = "flag"                      # "flag": report in output.health; "raise": SampleHealthError after the call
+        # None: only non-finite values make a scene bad.  A float: a finite |latent| above it does too.  There is NO default threshold:
+        # nobody has measured the latent range of trained weights on this path.
+        self.health_absmax: Optional[float] = None
 
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
@@ -208,8 +245,10 @@ class StableDiffusionBEVControlNetPipeline:
             raise RuntimeError("If you fixed the logic for generator, please remove this. Otherwise, please use other sampler.")
         return {"eta": eta} if "eta" in params else {}
 
-    def decode_latents(self, latents):
-        """pipeline_bev_controlnet.py:100-112 (5-D latents); VAE is a caller-supplied torch module."""
+    def decode_latents(self, latents, _records=None):
+        """pipeline_bev_controlnet.py:100-112 (5-D latents); VAE is a caller-supplied torch module.
+        _records: a list that receives the device-side health records [views, 4] of the decoded tensor (before the clamp, which would
+        turn +-Inf into valid pixels); not part of the reference signature."""
         if self.vae is None:
             raise ValueError("no VAE attached: use output_type='latent' or pass vae= to the pipeline")
         sf = getattr(getattr(self.vae, "config", None), "scaling_factor", 0.18215)
@@ -217,9 +256,43 @@ class StableDiffusionBEVControlNetPipeline:
         x = (latents / sf).reshape(-1, *latents.shape[2:])
         vdt = next(self.vae.parameters()).dtype
         image = self.vae.decode(x.to(vdt)).sample
+        if _records is not None:
+            _records.append(self._image_records(image))
         image = image.reshape(bs, -1, *image.shape[1:])
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.cpu().permute(0, 1, 3, 4, 2).float().numpy()
+
+    @staticmethod
+    def _image_records(image: torch.Tensor) -> torch.Tensor:
+        """fp32 [views, 4] health records of a decoded image tensor [views, 3, H, W] (ops.GroupStats, one group per view), on its device.
+        16-bit and fp32 tensors go through the kernel as they are; the launch is on the current stream, behind the decode."""
+        from .. import ops as O
+        if image.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise TypeError(f"health records of a {image.dtype} image: the kernel reads fp32, bf16 or fp16")
+        if not image.is_cuda:
+            raise RuntimeError("health records are computed on the MI355X only: the decoded image is not a device tensor")
+        image = image.contiguous()
+        rec = torch.zeros(image.shape[0], 4, dtype=torch.float32, device=image.device)
+        O.run_ops([O.GroupStats(image, rec, name="health.image")])
+        return rec
+
+    def _sample_health(self, mode: str, table: np.ndarray, b: int, n_cam: int, image_rec: Optional[np.ndarray]) -> SampleHealth:
+        """Host side of pipe.health: table [rows, b * n_cam, 4] (rows = n_steps for "trace", 1 for "final"), image_rec [b * n_cam, 4] or None."""
+        table = table.reshape(table.shape[0], b, n_cam, 4)
+        bad = table[..., 0] > 0                                                 # [rows, b, n_cam]
+        if self.health_absmax is not None:
+            bad = bad | (table[..., 1] > float(self.health_absmax))
+        bad_scene_step = bad.any(axis=2)                                        # [rows, b]
+        ok = ~bad_scene_step.any(axis=0)
+        first = None
+        if mode == "trace":
+            first = [int(np.argmax(bad_scene_step[:, i])) if bad_scene_step[:, i].any() else -1 for i in range(b)]
+        img_nf = None
+        if image_rec is not None:
+            img_nf = image_rec.reshape(b, n_cam, 4)[..., 0].astype(np.int64)
+            ok = ok & ~(img_nf > 0).any(axis=1)
+        return SampleHealth(ok=[bool(v) for v in ok], first_bad_step=first, final=table[-1].copy(), trace=table.copy() if mode == "trace" else None,
+                            image_nonfinite=img_nf)
 
     @staticmethod
     def numpy_to_pil_double(images):
@@ -246,6 +319,16 @@ class StableDiffusionBEVControlNetPipeline:
             n = int(n)
             cap = -(-int(L_box) // n) * n
         return (cap, "scene", (cap, "scene")) if scene else (cap, True, (cap, "dynamic"))
+
+    def _plan_key(self, n_scene, chunk, do_cfg, box_key, h, w, n_steps, guidance_scale, conditioning_scale, n_text, sched_kind, gv_mode, pdt, fork,
+                  health=None):
+        """Cache key of one scene chunk's SamplerPlan.  `health` enters as a trailing entry only when it is on: with the switch off the key is,
+        entry for entry, what it was before the switch existed."""
+        key = (n_scene, chunk, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(conditioning_scale), n_text, sched_kind,
+               gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
+        if health is not None:
+            key = key + (("health", health),)
+        return key
 
     def _plan_config(self) -> Dict[str, Any]:
         """Architecture config of the sampler plan: the UNet's, with the conditioning encoders' geometry taken from the ControlNet."""
@@ -287,6 +370,11 @@ class StableDiffusionBEVControlNetPipeline:
             raise NotImplementedError(f"{type(self.scheduler).__name__}: fused steps exist for magicdrive_amd.schedulers.DDIMScheduler and UniPCMultistepScheduler")
         if self._device.type != "cuda":
             raise RuntimeError("pipeline.to('cuda') first: the sampler has no CPU path")
+        health = getattr(self, "health", None)
+        if health not in (None, "final", "trace"):
+            raise ValueError(f"health={health!r}: None, 'final' or 'trace'")
+        if health is not None and self.health_action not in ("flag", "raise"):
+            raise ValueError(f"health_action={self.health_action!r}: 'flag' or 'raise'")
         if output_type != "latent" and self.vae is None:      # fail BEFORE the sampling loop, not after it
             raise ValueError("no VAE attached: use output_type='latent', pass vae= to the pipeline, or build it with from_pretrained(<sd15 dir>)")
         device = self._device
@@ -371,8 +459,8 @@ class StableDiffusionBEVControlNetPipeline:
             # the packed nets' identity and 16-bit type are part of the key: `pipe.unet.to(torch.float16)` re-packs the weights, and a plan
             # built on the old PackedNet would keep running (and keep alive) the old ones
             # box_bucket: the key carries (capacity, "dynamic") in the place of L_box, scene_boxes (capacity, "scene"); neither / no boxes: today's key
-            key = (s1 - s0, ci, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(controlnet_conditioning_scale), text.shape[1], sched_kind,
-                   gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
+            key = self._plan_key(s1 - s0, ci, do_cfg, box_key, h, w, n_steps, guidance_scale, controlnet_conditioning_scale, text.shape[1], sched_kind,
+                                 gv_mode, pdt, fork, health)
             plan = self._plans.get(key)
             if plan is None:
                 with torch.cuda.device(device):
@@ -383,7 +471,7 @@ class StableDiffusionBEVControlNetPipeline:
                     plan = SamplerPlan(plan_cfg, self.unet.packed(), self.controlnet.packed(), device, s1 - s0, do_cfg, L_plan, (h, w),
                                        num_steps=n_steps, guidance_scale=guidance_scale,
                                        conditioning_scale=float(controlnet_conditioning_scale), n_text=text.shape[1], scheduler_kind=sched_kind,
-                                       given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes)
+                                       given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes, **({} if health is None else {"health": health}))
                     plan.compile()
                 self._plans.put(key, plan)
             plan.load_inputs(latents[s0:s1], rows(camera_param, s0, s1), rows(text, s0, s1), rows(image, s0, s1),
@@ -417,18 +505,35 @@ class StableDiffusionBEVControlNetPipeline:
                     bar.update()
                     if callback is not None and i % callback_steps == 0:
                         callback(i, t, plans[0].latents().to(prompt_embeds.dtype))
+            if health == "final":                             # one record launch per chunk, on the chunk's stream, behind its last step
+                for plan, st in zip(plans, sts):
+                    plan.run_health(st)
             for s_ in side_all:                               # the caller's stream owns the result: join the side streams into it
                 done = torch.cuda.Event()
                 done.record(s_)
                 main.wait_event(done)
             latents = (plans[0].latents() if n_chunk == 1 else torch.cat([pl.latents_on(main) for pl in plans])).to(prompt_embeds.dtype)
+            health_dev = None
+            if health is not None:                            # still on the device: the chunks' tables side by side, scenes in call order
+                with torch.cuda.stream(main):
+                    health_dev = torch.cat([pl.health_table() for pl in plans], dim=1).reshape(-1)
+        image_rec = [] if (health is not None and output_type != "latent") else None
         if output_type == "latent":
             out, nsfw = latents, None
         else:
-            out = self.decode_latents(latents)
+            out = self.decode_latents(latents, **({} if image_rec is None else {"_records": image_rec}))
             nsfw = None
             if output_type == "pil":
                 out = self.numpy_to_pil_double(out)
-        if not return_dict:
-            return (out, nsfw)
-        return BEVStableDiffusionPipelineOutput(images=out, nsfw_content_detected=nsfw)
+        report = None
+        if health is not None:
+            # ONE device-to-host copy for everything: [latent records | image records]
+            with torch.cuda.device(device):
+                packed = (torch.cat([health_dev] + [r.reshape(-1) for r in image_rec]) if image_rec else health_dev).cpu().numpy()
+            n_lat = health_dev.numel()
+            report = self._sample_health(health, packed[:n_lat].reshape(-1, b * n_cam, 4), b, n_cam,
+                                         packed[n_lat:].reshape(b * n_cam, 4) if image_rec else None)
+        result = (out, nsfw) if not return_dict else BEVStableDiffusionPipelineOutput(images=out, nsfw_content_detected=nsfw, health=report)
+        if report is not None and self.health_action == "raise" and report.bad_scenes:
+            raise SampleHealthError(report.bad_scenes, health=report, output=result)
+        return result

@@ -124,9 +124,11 @@ def encode_given_views(pipe, pixel_values: torch.Tensor) -> torch.Tensor:
     return lat.reshape(b, n, *lat.shape[1:])
 
 
-def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, generator=None, fix_seed_for_every_generation: bool = False):
+def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, generator=None, fix_seed_for_every_generation: bool = False,
+                      full_output: bool = False):
     """run_one_batch_pipe_given_view (demo/run_cond_on_view.py:34-120): `validation_times - 1` generations, generation `ti` with the
-    encoded ground-truth view `ti` of every scene given and the other views sampled.  Yields (ti, images: List[List[PIL]])."""
+    encoded ground-truth view `ti` of every scene given and the other views sampled.  Yields (ti, images: List[List[PIL]]);
+    full_output: (ti, the pipeline's output object) instead (--health reads its .health)."""
     if pixel_values is None:
         raise ValueError("--cond-on-view needs the ground-truth views (`img`) in the samples")
     latents = encode_given_views(pipe, pixel_values)
@@ -137,7 +139,8 @@ def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, gen
             conditional_latents[b][ti] = latents[b, ti]
         if run["seed"] is not None and fix_seed_for_every_generation:
             generator = torch.Generator().manual_seed(run["seed"])         # :97-99
-        yield ti, pipe(conditional_latents=conditional_latents, generator=generator, **kw).images
+        out = pipe(conditional_latents=conditional_latents, generator=generator, **kw)
+        yield ti, (out if full_output else out.images)
 
 
 def build_pipe(ckpt: str, sd15: str, scheduler: str, device, given_view: bool = False, hip_text_encoder: bool = False):
@@ -209,13 +212,27 @@ def save_views(out_dir: str, scene: int, gen: int, views) -> List[str]:
     return names
 
 
-def exchange_batch(records: List[Dict], images, rank: int, world: int, gather_images: bool, out_dir: str) -> List[Dict]:
+def health_fields(health, bi: int) -> Dict:
+    """The index.json entries of scene `bi` of one pipeline call from its output.health (pipeline_bev_controlnet.SampleHealth): ok, the step
+    the scene died at (-1: never), the non-finite values of its final latents plus decoded pixels, the largest finite |latent|."""
+    nonfinite = int(health.final[bi, :, 0].sum())
+    if health.image_nonfinite is not None:
+        nonfinite += int(health.image_nonfinite[bi].sum())
+    first = -1 if health.first_bad_step is None else int(health.first_bad_step[bi])
+    return dict(ok=bool(health.ok[bi]), first_bad_step=first, nonfinite=nonfinite, absmax=float(health.final[bi, :, 1].max()))
+
+
+def exchange_batch(records: List[Dict], images, rank: int, world: int, gather_images: bool, out_dir: str, skip_bad: bool = False) -> List[Dict]:
     """End of a batch on every rank (val_set_gen.py:137-151).  records: this rank's [{scene, gen, rank, seed}], images: the matching
     [views] lists.  Single-node branch: the rank writes its own files, then the labels are gathered; multi-node branch (gather_images): labels
     AND uint8 images are gathered and rank 0 writes.  Returns the records with their file names — on rank 0 those of every rank, elsewhere []
-    (ddp_utils.concat_from_everyone).  One all_gather_object per batch; ranks whose shard ran out contribute an empty list."""
+    (ddp_utils.concat_from_everyone).  One all_gather_object per batch; ranks whose shard ran out contribute an empty list.
+    skip_bad (--health skip): a record with ok == False keeps its place in the index with files = [], and none of its views is written or sent;
+    the health fields are part of the records, so they ride on the same exchange."""
     import numpy as np
     import torch.distributed as dist
+    if skip_bad:
+        images = [[] if r_.get("ok") is False else views for r_, views in zip(records, images)]
     if not gather_images:
         for r_, views in zip(records, images):
             r_["files"] = save_views(out_dir, r_["scene"], r_["gen"], views)
@@ -258,6 +275,9 @@ def main(argv=None):
     ap.add_argument("--scene-boxes", action="store_true", help="every scene of a batch attends to its own boxes only (pipe.scene_boxes, INTEGRATION.md §1): "
                     "with fix_seed_within_batch=true a scene's pictures are those of the reference's batch-1 run at any --batch-size; default: the "
                     "reference's padded-batch semantics")
+    ap.add_argument("--health", choices=["off", "flag", "skip"], default="off", help="per-scene sample health from the device-side records (pipe.health = 'trace', "
+                    "INTEGRATION.md §1).  flag: index.json gains ok / first_bad_step / nonfinite / absmax per scene and generation; skip: also, the PNGs of "
+                    "a bad scene are not written.  Either ends with a one-line summary and exit status 3 if any scene was bad.  off (default): nothing changes")
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args(argv)
     from magicdrive_amd.dataset import FolderSet
@@ -278,6 +298,9 @@ def main(argv=None):
         pipe.box_bucket = a.box_bucket
     if a.scene_boxes:
         pipe.scene_boxes = True
+    health_on = a.health != "off"
+    if health_on:
+        pipe.health, pipe.health_action = "trace", "flag"
     data = FolderSet(a.data)
     if rank == 0:
         os.makedirs(a.out, exist_ok=True)
@@ -289,6 +312,7 @@ def main(argv=None):
     n_rounds = (len(batches) + world - 1) // world                  # every rank takes part in every per-batch exchange (a collective)
     index: List[Dict] = []
     n_local = 0
+    n_bad_local = 0
     it = iter_pipe_kwargs(data, run, a.batch_size, with_pixels=a.cond_on_view, only=mine)
     for rnd in range(n_rounds):
         j = rnd * world + rank
@@ -310,26 +334,37 @@ def main(argv=None):
             gen = batch_generator(seed, bs, run["fix_seed_within_batch"], global_gen)
             base_gen = gen[0] if isinstance(gen, list) else gen
             if a.cond_on_view:
-                for ti, images in cond_on_view_runs(pipe, kw, pixel_values, run, generator=base_gen):
-                    for bi, views in enumerate(images):
-                        records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed)); images_out.append(views)
+                for ti, out in cond_on_view_runs(pipe, kw, pixel_values, run, generator=base_gen, full_output=health_on):
+                    for bi, views in enumerate(out.images if health_on else out):
+                        records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed, **(health_fields(out.health, bi) if health_on else {})))
+                        images_out.append(views)
             else:
                 for ti in range(run["validation_times"]):
                     g = gen
                     if a.reseed_per_run and base_gen is not None:
                         g1 = torch.Generator().manual_seed(new_local_seed(base_gen))
                         g = [g1] * bs if run["fix_seed_within_batch"] else g1
-                    images = pipe(generator=g, **kw).images                      # List[List[PIL]]: scene x view
-                    for bi, views in enumerate(images):
-                        records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed)); images_out.append(views)
+                    out = pipe(generator=g, **kw)
+                    for bi, views in enumerate(out.images):                       # List[List[PIL]]: scene x view
+                        records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed, **(health_fields(out.health, bi) if health_on else {})))
+                        images_out.append(views)
             n_local += bs
-        index += exchange_batch(records, images_out, rank, world, a.gather_images, a.out)
+        n_bad_local += sum(1 for r_ in records if r_.get("ok") is False)
+        index += exchange_batch(records, images_out, rank, world, a.gather_images, a.out, skip_bad=a.health == "skip")
     if rank == 0:
         index.sort(key=lambda r_: (r_["scene"], r_["gen"]))
         with open(os.path.join(a.out, "index.json"), "w") as f:
             json.dump(dict(world=world, seed=run["seed"], gather_images=bool(a.gather_images), generations=index), f, indent=1)
         print(f"sampled {len(data)} scenes x {run['validation_times'] - (1 if a.cond_on_view else 0)} on {world} rank(s) -> {a.out}")
+    n_bad = n_bad_local
+    if health_on and rank == 0:
+        bad = [r_ for r_ in index if r_.get("ok") is False]
+        n_bad = len(bad)
+        print(f"health: {n_bad} of {len(index)} generations bad" + (f" (scenes {sorted({r_['scene'] for r_ in bad})}"
+              + (", pictures not written" if a.health == "skip" else "") + ")" if bad else ""))
     DD.shutdown()
+    if health_on and n_bad:
+        sys.exit(3)
 
 
 if __name__ == "__main__":
