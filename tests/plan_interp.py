@@ -246,7 +246,21 @@ def run_softmax(op: O.Softmax):
     op.Y[:, :op.T].copy_(y.to(op.Y.dtype))
 
 
-DISPATCH = {O.Gemm: run_gemm, O.Conv: run_conv, O.Attn: run_attn, O.GroupNorm: run_groupnorm, O.LayerNorm: run_layernorm,
+def run_group_stats(op: O.GroupStats):
+    """MdxStatsDesc: {nonfinite, absmax, sum, sumsq} per group over the finite elements; with `row`, into that row of the table, or nowhere."""
+    x = op.X.float().reshape(op.X.shape[0], -1)
+    fin = torch.isfinite(x)
+    xz = torch.where(fin, x, torch.zeros_like(x))
+    rec = torch.stack([(~fin).sum(1).float(), xz.abs().amax(1), xz.sum(1), (xz * xz).sum(1)], -1)
+    if op.row is not None:
+        r = int(op.row.item())
+        if 0 <= r < op.out.shape[0]:
+            op.out[r].copy_(rec)
+    else:
+        (op.out[0] if op.out.dim() == 3 else op.out).copy_(rec)
+
+
+DISPATCH = {O.Gemm: run_gemm, O.GroupStats: run_group_stats, O.Conv: run_conv, O.Attn: run_attn, O.GroupNorm: run_groupnorm, O.LayerNorm: run_layernorm,
             O.Ew: run_ew, O.Upsample: run_upsample, O.Layout: run_layout, O.Fourier: run_fourier, O.Gather: run_gather,
             O.TimeEmb: run_timeemb, O.DdimStep: run_ddim, O.UniPCStep: run_unipc, O.Softmax: run_softmax}
 

@@ -1253,6 +1253,9 @@ def applicable(c, mut):
 
 
 ABS_BOUND = dict(timeemb=2e-4, ddim=1e-5)      # fp32 outputs held to the absolute bounds of tests/test_kernels_gpu.py instead of close()
+F32_REL_L2 = 2e-5             # fp32 GEMM / conv outputs: rel L2 against fp64 (test_kernels_gpu.py::test_conv_out_weight_stationary's bound, tests/test_tails_gpu.py)
+ROWSTAT_BOUND = 2e-5          # MdxGemmDesc.rowstat_out: |sum - fp64 sum of the stored C| / (|sum| + 1) (test_kernels_gpu.py::test_gemm_row_statistics_out)
+UNIPC_ATOL_REL = 3e-5         # UniPC latents: atol = this x max |ref| (test_kernels_gpu.py::test_cfg_unipc_matches_oracle_scheduler)
 
 
 def store_dtype(c, dtype):

@@ -115,7 +115,7 @@ def verdict(tally, c, outs_by_poison, refs, boxes_ok, kern, residual_bound=None)
             continue
         if x.dtype == F32:
             rel = V.rel_l2(x, r)
-            if not rel < 2e-5:
+            if not rel < T.F32_REL_L2:
                 tally.fails.append((lab, f"fp32 output {i}: rel_l2 {rel:.3e} >= 2e-5"))
             continue
         w, rel = tally.add(x, r)
@@ -245,7 +245,7 @@ def test_gemm_tails(dev, family, dtype):
             nt = -(-c["N"] // 128) if c["tag"].startswith("gemm_ws") else 1          # rowstat_kernel: part 0 = whole rows, the rest zeros
             want = rowstat_ref(C, [(128 * k, min(c["N"], 128 * k + 128)) for k in range(nt)] if c["tag"].startswith("gemm_ws") else [(0, c["N"])])
             err = float(((st[:nt] - want).abs() / (want.abs() + 1.0)).max()) if bool(torch.isfinite(st).all()) else math.inf
-            if not (err < 2e-5 and bool((st[nt:] == 0).all())):
+            if not (err < T.ROWSTAT_BOUND and bool((st[nt:] == 0).all())):
                 tally.fails.append((T.label(c), f"row statistics: {err:.3e} (bound 2e-5), unused parts zero: {bool((st[nt:] == 0).all())}"))
     tally.done()
 
