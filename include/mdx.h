@@ -483,6 +483,44 @@ typedef struct MdxStatsDesc {
 } MdxStatsDesc;
 int mdx_group_stats_bf16(const MdxStatsDesc* d, void* stream);
 
+/*
+ * mdx_sdpa_bf16 / _f16 — scaled-dot-product attention on Q, K and V as a projection writes them, for any sequence length (additive symbols,
+ * the ABI version stays 12; MDX_OP_SDPA; csrc/attention_vrow.hip; mdx_last_kernel() starts with "attn_vrow_kernel<").  V is read ROW-MAJOR,
+ * in place: no V^T operand, no padded key axis.  mdx_attention_* and its routes are unchanged and never come here.
+ *   Q [B][Tq][H*d], K [B][Tk][H*d], V [B][Tk][H*d], O [B][Tq][H*d], 16-bit: element (b,t,h,j) of X at X + b*sX + t*ldx + h*d + j (element
+ *   strides).  Batch b of Q attends to batch b of K / V.
+ * Result: O[b,q,h,:] = softmax_j(scale * Q[b,q,h,:] . K[b,j,h,:] + mask) . V[b,j,h,:].  Softmax in fp32 with exp2: the scores are scaled, then
+ *   masked, and the maximum is taken of the scaled values (Tk == 1 returns V[b,0] and causal row 0 returns V[b,0] bit for bit); P is rounded to
+ *   the storage type before the PV product, the row sum is taken of the unrounded values (as mdx_attention_*).
+ * Shapes: any Tq, Tk >= 1; Tq != Tk is allowed without causal.  d % 8 == 0, d <= 160 and ceil(d / 16) in {1..6, 8, 10} (the instance set of
+ *   mdx_attention_*); any other d returns MDX_EUNSUPPORTED, the message names d.
+ * Aliasing: Q, K and V may be the column blocks of one [B][T][3*H*d] buffer (ldq = ldk = ldv = 3*H*d).  O must not alias them.
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): Q, K, V, O not NULL; Q, K, V 16-byte aligned, ldq, ldk, ldv, sQ, sK, sV multiples
+ *   of 8; O 8-byte aligned, ldo, sO multiples of 4; ldq, ldk, ldv, ldo >= H*d; klen_dev 4-byte aligned; B, H, Tq, Tk fit a 32-bit int and
+ *   are not negative; causal in {0, 1}; causal == 1 needs Tq == Tk.
+ * causal == 1: key j is visible to query i iff j <= i.
+ * klen_dev: NULL, or int32 [B] on the device: batch b attends to keys [0, klen_dev[b]); with causal, key j is visible iff j <= i and
+ *   j < klen_dev[b].  The counts are read when the kernel RUNS, so a replayed graph sees a value written since capture.  A count outside
+ *   [1, Tk] writes NaN to every O row of that batch and to no other batch (the convention of MdxAttnDesc.tk_dev).  A batch with the full
+ *   count Tk has the bits of the klen_dev == NULL call.
+ * Memory safety: the kernel never reads a K or V row at or past Tk (with klen_dev: at or past the count) of its batch; the tail rows of a
+ *   staged tile are loaded from a clamped row and zeroed, so a pad row contributes 0 * 0, never 0 * garbage.  All addressing is 64-bit.
+ * Range: the PV product accumulates un-normalised in fp32 (sum_j p_j v_j with p_j <= 1, up to Tk terms), as in mdx_attention_*: |V| * Tk
+ *   must stay below the fp32 maximum.  Every fp16 value qualifies; bf16 values within a factor Tk of the type's maximum can overflow to Inf.
+ * Empty calls: B, H, Tq or Tk equal to 0 launches nothing and returns MDX_OK (after the checks above).
+ * Determinism: the summation order is fixed; the bits of batch b's rows depend on batch b's operands alone, not on B and not on the
+ *   waves per workgroup the launcher picks.
+ */
+typedef struct MdxSdpaDesc {
+    const void* Q; const void* K; const void* V; void* O;
+    const int32_t* klen_dev;
+    int64_t B, H, Tq, Tk, d;
+    int64_t ldq, sQ, ldk, sK, ldv, sV, ldo, sO;
+    double scale;
+    int64_t causal;
+} MdxSdpaDesc;
+int mdx_sdpa_bf16(const MdxSdpaDesc* d, void* stream);
+
 /* ---- program = array of ops, executed in order on one stream ------------ */
 #define MDX_OP_GEMM 1
 #define MDX_OP_CONV 2
@@ -500,6 +538,7 @@ int mdx_group_stats_bf16(const MdxStatsDesc* d, void* stream);
 #define MDX_OP_ATTN_ROWS 14   /* MdxAttnDesc through mdx_attention_ctx_rows_*: tk_dev -> int32 [B] */
 #define MDX_OP_GROUPNORM_RESIDENT 15   /* MdxGroupNormDesc through mdx_groupnorm_resident_* */
 #define MDX_OP_GROUP_STATS 16          /* MdxStatsDesc through mdx_group_stats_* */
+#define MDX_OP_SDPA 17                 /* MdxSdpaDesc through mdx_sdpa_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -532,6 +571,7 @@ int mdx_cfg_unipc_step_f16(const MdxUniPCDesc* d, void* stream);
 int mdx_softmax_rows_f16(const MdxSoftmaxDesc* d, void* stream);
 int mdx_attention_ctx_rows_f16(const MdxAttnDesc* d, void* stream);
 int mdx_group_stats_f16(const MdxStatsDesc* d, void* stream);
+int mdx_sdpa_f16(const MdxSdpaDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -110,6 +110,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
             case MDX_OP_SOFTMAX: return mdx_softmax_rows_f16((const MdxSoftmaxDesc*)d, st);
             case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_f16((const MdxAttnDesc*)d, st);
             case MDX_OP_GROUP_STATS: return mdx_group_stats_f16((const MdxStatsDesc*)d, st);
+            case MDX_OP_SDPA: return mdx_sdpa_f16((const MdxSdpaDesc*)d, st);
             default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
         }
     }
@@ -131,6 +132,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
         case MDX_OP_SOFTMAX: return mdx_softmax_rows((const MdxSoftmaxDesc*)d, st);
         case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_bf16((const MdxAttnDesc*)d, st);
         case MDX_OP_GROUP_STATS: return mdx_group_stats_bf16((const MdxStatsDesc*)d, st);
+        case MDX_OP_SDPA: return mdx_sdpa_bf16((const MdxSdpaDesc*)d, st);
         default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
     }
 }

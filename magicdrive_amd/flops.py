@@ -19,6 +19,8 @@ def kernel_family(op) -> str:
         return "gemm_conv_kernel<gemm>"
     if isinstance(op, O.Attn):
         return "attn_kernel"
+    if isinstance(op, O.Sdpa):
+        return "attn_vrow_kernel"
     if isinstance(op, O.GroupNorm):
         return "groupnorm_kernel"
     if isinstance(op, O.LayerNorm):
@@ -27,6 +29,8 @@ def kernel_family(op) -> str:
 
 
 def op_flops(op) -> float:
+    """Algorithmic FLOPs of one op (2 per MAC).  Attention counts QK^T + PV over every (query, key) pair: 4 * B * Tq * Tk * H * d;
+    ops.Sdpa with `causal` counts half of that (the masked pairs above the diagonal are not work the algorithm asks for)."""
     if isinstance(op, O.Gemm):
         C = op.C
         batch = C.shape[0] if C.dim() == 3 else 1
@@ -49,6 +53,12 @@ def op_flops(op) -> float:
             if present != B * op.nsrc:
                 return 4.0 * present * Tq * op.Tk * C
         return 4.0 * B * Tq * op.Tk * C * op.nsrc          # QK^T + PV
+    if isinstance(op, O.Sdpa):
+        # convention: QK^T + PV over every (query, key) pair, 4 * B * Tq * Tk * H * d; under `causal` half of it (the pairs above the
+        # diagonal are masked: T (T + 1) / 2 of T^2 pairs, counted as T^2 / 2).  A key count (klen) lives on the device and is not counted.
+        B, Tq, C = op.Q.shape
+        f = 4.0 * B * Tq * op.K.shape[1] * C
+        return f / 2 if op.causal else f
     return 0.0
 
 
@@ -62,6 +72,8 @@ def op_bytes(op) -> float:
         return nb(op.X) + nb(op.Wt) + nb(op.Y) + nb(op.R)
     if isinstance(op, O.Attn):
         return nb(op.Q) + op.nsrc * (nb(op.K) + op.K.shape[0] * op.K.shape[2] * op.Tk * 2) // max(op.nsrc, 1) + nb(op.O)
+    if isinstance(op, O.Sdpa):
+        return nb(op.Q) + nb(op.K) + nb(op.V) + nb(op.O)
     if isinstance(op, (O.GroupNorm, O.LayerNorm)):
         return nb(op.X) + nb(op.Y)
     if isinstance(op, (O.Ew, O.Upsample, O.Layout)):

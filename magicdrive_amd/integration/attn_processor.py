@@ -69,3 +69,47 @@ class MdxAttnProcessor:
         o = o.to(hidden_states.dtype)
         return attn.to_out[1](attn.to_out[0](o))
 # attn.set_processor(MdxAttnProcessor())   — same call site as set_use_memory_efficient_attention_xformers (:176-292)
+
+
+class MdxSdpaDesc(ctypes.Structure):               # mirrors include/mdx.h MdxSdpaDesc field for field
+    _fields_ = [(n, ctypes.c_void_p) for n in "Q K V O klen_dev".split()] + \
+               [(n, ctypes.c_int64) for n in "B H Tq Tk d ldq sQ ldk sK ldv sV ldo sO".split()] + \
+               [("scale", ctypes.c_double), ("causal", ctypes.c_int64)]
+
+
+def _mdx_sdpa(name):
+    fn = getattr(_mdx(), name)
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    return fn
+
+
+class MdxSdpaProcessor:
+    """The same protocol on mdx_sdpa_* (csrc/attention_vrow.hip): the kernel reads V row-major, so the to_q / to_k / to_v outputs go to it
+    as they are — no V^T tensor, no padded key axis, no extra pass over V.  fp16 and bf16 modules run in their own type; any other
+    dtype is cast to bf16 (as MdxAttnProcessor does)."""
+
+    def __call__(self, attn, hidden_states, encoder_hidden_states=None, attention_mask=None, temb=None):
+        if attention_mask is not None:
+            raise NotImplementedError("MagicDrive's sampler never passes an attention mask (blocks.py:144-238); the library's masks are "
+                                      "MdxSdpaDesc.causal and MdxSdpaDesc.klen_dev (a key count per batch)")
+        if not hidden_states.is_cuda:
+            raise RuntimeError("MdxSdpaProcessor runs on the GPU kernel; there is no CPU path")
+        ctx = hidden_states if encoder_hidden_states is None else encoder_hidden_states
+        f16 = hidden_states.dtype == torch.float16
+        dt = torch.float16 if f16 else torch.bfloat16
+        q = attn.to_q(hidden_states).to(dt)                                       # [B, Tq, C]
+        k = attn.to_k(ctx).to(dt)                                                 # [B, Tk, C]
+        v = attn.to_v(ctx).to(dt)                                                 # [B, Tk, C], row-major: read in place
+        o = torch.empty_like(q)
+        d = MdxSdpaDesc(Q=q.data_ptr(), K=k.data_ptr(), V=v.data_ptr(), O=o.data_ptr(), B=q.shape[0], H=attn.heads,
+                        Tq=q.shape[1], Tk=k.shape[1], d=q.shape[2] // attn.heads, ldq=q.stride(1), sQ=q.stride(0),
+                        ldk=k.stride(1), sK=k.stride(0), ldv=v.stride(1), sV=v.stride(0), ldo=o.stride(1), sO=o.stride(0),
+                        scale=float(attn.scale), causal=0)
+        with torch.cuda.device(q.device):
+            rc = _mdx_sdpa("mdx_sdpa_f16" if f16 else "mdx_sdpa_bf16")(ctypes.byref(d), ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream))
+        if rc:
+            raise RuntimeError((_mdx().mdx_last_error() or b"").decode())
+        o = o.to(hidden_states.dtype)
+        return attn.to_out[1](attn.to_out[0](o))
+# attn.set_processor(MdxSdpaProcessor())

@@ -669,6 +669,70 @@ class GroupStats:
         return self.opcode, d
 
 
+@dataclass
+class Sdpa:
+    """O = softmax(scale * Q K^T + mask) V on Q, K and V as a projection writes them (MdxSdpaDesc, csrc/attention_vrow.hip): Q, O
+    [B,Tq,H*d], K, V [B,Tk,H*d], 16-bit views with unit inner stride — e.g. the three column blocks of one [B,T,3C] buffer.  V is read
+    row-major, in place, at any length.  causal: key j is visible to query i iff j <= i (needs Tq == Tk).  klen: int32 [B] on the device,
+    read when the kernel runs — batch b attends to its first klen[b] keys; a count outside [1, Tk] writes NaN to that batch's rows."""
+    Q: torch.Tensor
+    K: torch.Tensor
+    V: torch.Tensor
+    O: torch.Tensor
+    heads: int
+    scale: float
+    causal: bool = False
+    klen: Optional[torch.Tensor] = None      # int32 [B], same device as Q
+    name: str = ""
+    opcode = L.OP_SDPA
+
+    def lower(self):
+        Q, K, V, O = self.Q, self.K, self.V, self.O
+        _chk(all(t.dim() == 3 for t in (Q, K, V, O)), f"sdpa {self.name}: Q, K, V, O must be [B, T, H*d]")
+        B, Tq, Cc = Q.shape
+        Tk = K.shape[1]
+        _chk(Q.dtype in H16 and K.dtype == Q.dtype and V.dtype == Q.dtype and O.dtype == Q.dtype, f"sdpa {self.name}: one 16-bit type for Q, K, V, O")
+        _chk(all(t.shape[2] == 1 or t.stride(2) == 1 for t in (Q, K, V, O)), f"sdpa {self.name}: inner strides")
+        _chk(self.heads > 0 and Cc % self.heads == 0, f"sdpa {self.name}: C={Cc} is not a multiple of heads={self.heads}")
+        _chk(tuple(K.shape) == (B, Tk, Cc) and tuple(V.shape) == (B, Tk, Cc) and O.shape == Q.shape,
+             f"sdpa {self.name}: shapes Q{tuple(Q.shape)} K{tuple(K.shape)} V{tuple(V.shape)} O{tuple(O.shape)}")
+        _chk(not self.causal or Tq == Tk, f"sdpa {self.name}: causal needs Tq == Tk (Tq={Tq}, Tk={Tk})")
+        d = L.MdxSdpaDesc()
+        d.Q, d.K, d.V, d.O = _p(Q), _p(K), _p(V), _p(O)
+        d.B, d.H, d.Tq, d.Tk, d.d = B, self.heads, Tq, Tk, Cc // self.heads
+        d.ldq, d.sQ = Q.stride(1), Q.stride(0)
+        d.ldk, d.sK = K.stride(1), K.stride(0)
+        d.ldv, d.sV = V.stride(1), V.stride(0)
+        d.ldo, d.sO = O.stride(1), O.stride(0)
+        d.scale, d.causal = float(self.scale), int(self.causal)
+        if self.klen is not None:
+            _chk(self.klen.dtype == torch.int32 and self.klen.dim() == 1 and self.klen.numel() == B and self.klen.is_contiguous()
+                 and self.klen.device == Q.device, f"sdpa {self.name}: klen must be int32 [B={B}], contiguous, on the device of Q")
+            d.klen_dev = _p(self.klen)
+        return self.opcode, d
+
+
+def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, scale: Optional[float] = None, causal: bool = False,
+         key_lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(scale * q k^T + mask) v per head on the GPU kernel behind mdx_sdpa_* (ops.Sdpa), on torch's current stream.
+    q [B,Tq,H*d], k, v [B,Tk,H*d]: bf16 or fp16 tensors or strided views with unit inner stride (the column blocks of a fused projection
+    buffer are passed as they are: nothing is copied).  scale defaults to d ** -0.5; key_lengths is int32 [B] on the device.  Returns
+    `out`, or a new [B,Tq,H*d] tensor."""
+    for t in (q, k, v):
+        if t.dtype not in H16:
+            raise TypeError(f"ops.sdpa takes bfloat16 or float16 tensors, got {t.dtype}")
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise RuntimeError("magicdrive_amd: ops.sdpa runs on the MI355X only (no CPU fallback)")
+    _chk(q.dim() == 3 and heads > 0 and q.shape[2] % heads == 0, f"sdpa: q must be [B, Tq, H*d] with H={heads}, got {tuple(q.shape)}")
+    if scale is None:
+        scale = (q.shape[2] // heads) ** -0.5
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    run_ops([Sdpa(q, k, v, out, heads=heads, scale=scale, causal=causal, klen=key_lengths)])
+    return out
+
+
 def dtype_code(op) -> int:
     """MdxOp.dtype of an IR op: fp16 when its 16-bit tensors are torch.float16, else bf16 (ops without 16-bit tensors run either build)."""
     for v in vars(op).values():
