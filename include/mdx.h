@@ -521,6 +521,44 @@ typedef struct MdxSdpaDesc {
 } MdxSdpaDesc;
 int mdx_sdpa_bf16(const MdxSdpaDesc* d, void* stream);
 
+/*
+ * mdx_latent_blend_bf16 / _f16 — keep known REGIONS of the latents while sampling: per-pixel, fractional masks for given views (additive
+ * symbols, the ABI version stays 12; MDX_OP_LATENT_BLEND; csrc/blend.hip; mdx_last_kernel() starts with "blend_kernel").  The per-pixel form of
+ * gv_mode 1 of MdxDdimDesc / MdxUniPCDesc (pipeline_bev_controlnet_given_view.py:283-295), as an op of its own placed BEHIND the scheduler
+ * op of a step; the scheduler descriptors are untouched.  The two builds differ only in the 16-bit type of x_in.
+ *   x     : fp32 [n] latents, the scheduler op's output, updated in place;
+ *   cond  : fp32 [n] known clean latents, noise : fp32 [n] initial noise, both in x's layout;
+ *   mask  : fp32 [n / mask_elems]: m = mask[i / mask_elems] belongs to element i (mask_elems = the channel count of an NHWC latent: one
+ *           value per latent pixel).  1 keeps the known latent, 0 keeps the sampler's, a fraction mixes.  The values are device data and
+ *           taken as they are; callers validate them (the pipeline does, on the host);
+ *   coef, step_ptr : the scheduler op's table and counter.  The scheduler op has already advanced *step_ptr, so the step just finished is
+ *           s = *step_ptr - 1, read when the kernel RUNS (a replayed hipGraph sees the current value).  s < 0 or s >= last_step writes
+ *           NOTHING: the last step's output stays the scheduler's, as in gv_mode 1.  Otherwise a = coef[s * coef_ld + col_a] and
+ *           sg = coef[s * coef_ld + col_s]: (alpha, sigma) of the NEXT timestep — columns 2, 3 of a DDIM row (coef_ld 4), 10, 11 of a
+ *           UniPC row (coef_ld 12).
+ * For every i < n, with t = a * cond[i] + sg * noise[i] (the expression of the schedulers' gv_mode 1 line, one helper in csrc/common.h:
+ * a mask of ones gives the bits of that path):
+ *   m == 0 : x[i] and its x_in copies are not touched (they keep the scheduler op's bits);
+ *   m == 1 : x[i] = t;
+ *   else   : x[i] = fmaf(m, t - x[i], x[i]).
+ * Every written element also refreshes x_in as the scheduler kernels do: xin_ld == 0: fp32, flat; xin_ld > 0: the build's 16-bit type,
+ * channels-last with pixel stride xin_ld (the pad channels are never written); cfg != 0: both [uncond | cond] halves.  x_in NULL: no copy.
+ * fp32 math, no atomics, 64-bit addressing.  16-byte accesses when x, cond, noise are 16-byte aligned and mask_elems % 4 == 0; any other
+ * case is SERVED by scalar accesses with the same bits.  Nothing is read or written past n elements, n / mask_elems mask entries, or the
+ * x_in pixels of n / xin_c rows (twice that many rows when cfg != 0).
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): x, cond, noise, mask, coef, step_ptr not
+ * NULL (x_in may be NULL); x, cond, noise, mask, coef, step_ptr 4-byte aligned, x_in at its element's alignment (4 / 2 bytes); n not
+ * negative; mask_elems >= 1 and divides n; 0 <= col_a, col_s < coef_ld; cfg in {0, 1}; xin_c, xin_ld, coef_ld, last_step fit a 32-bit int
+ * and xin_ld is not negative; xin_ld > 0 needs 0 < xin_c <= xin_ld and xin_c dividing n.  n == 0: MDX_OK (after the checks), nothing is
+ * launched.
+ */
+typedef struct MdxBlendDesc {
+    float* x; const float* cond; const float* noise; const float* mask; const float* coef;
+    const int32_t* step_ptr; void* x_in;
+    int64_t n, mask_elems, coef_ld, col_a, col_s, last_step, cfg, xin_c, xin_ld;
+} MdxBlendDesc;
+int mdx_latent_blend_bf16(const MdxBlendDesc* d, void* stream);
+
 /* ---- program = array of ops, executed in order on one stream ------------ */
 #define MDX_OP_GEMM 1
 #define MDX_OP_CONV 2
@@ -539,6 +577,7 @@ int mdx_sdpa_bf16(const MdxSdpaDesc* d, void* stream);
 #define MDX_OP_GROUPNORM_RESIDENT 15   /* MdxGroupNormDesc through mdx_groupnorm_resident_* */
 #define MDX_OP_GROUP_STATS 16          /* MdxStatsDesc through mdx_group_stats_* */
 #define MDX_OP_SDPA 17                 /* MdxSdpaDesc through mdx_sdpa_* */
+#define MDX_OP_LATENT_BLEND 18         /* MdxBlendDesc through mdx_latent_blend_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -572,6 +611,7 @@ int mdx_softmax_rows_f16(const MdxSoftmaxDesc* d, void* stream);
 int mdx_attention_ctx_rows_f16(const MdxAttnDesc* d, void* stream);
 int mdx_group_stats_f16(const MdxStatsDesc* d, void* stream);
 int mdx_sdpa_f16(const MdxSdpaDesc* d, void* stream);
+int mdx_latent_blend_f16(const MdxBlendDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -111,6 +111,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
             case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_f16((const MdxAttnDesc*)d, st);
             case MDX_OP_GROUP_STATS: return mdx_group_stats_f16((const MdxStatsDesc*)d, st);
             case MDX_OP_SDPA: return mdx_sdpa_f16((const MdxSdpaDesc*)d, st);
+            case MDX_OP_LATENT_BLEND: return mdx_latent_blend_f16((const MdxBlendDesc*)d, st);
             default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
         }
     }
@@ -133,6 +134,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
         case MDX_OP_ATTN_ROWS: return mdx_attention_ctx_rows_bf16((const MdxAttnDesc*)d, st);
         case MDX_OP_GROUP_STATS: return mdx_group_stats_bf16((const MdxStatsDesc*)d, st);
         case MDX_OP_SDPA: return mdx_sdpa_bf16((const MdxSdpaDesc*)d, st);
+        case MDX_OP_LATENT_BLEND: return mdx_latent_blend_bf16((const MdxBlendDesc*)d, st);
         default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
     }
 }

@@ -60,6 +60,19 @@ __device__ __forceinline__ bf16_t f2bf(float f) {
 }
 #endif
 
+// add_noise(cond, noise, t) = alpha_t cond + sigma_t noise: a known latent at the noise level of timestep t (scheduling_ddim.py /
+// scheduling_unipc_multistep.py add_noise).  ONE expression for the gv_mode 1 line of ddim_kernel / unipc_kernel (elementwise.hip) and for
+// blend_kernel (blend.hip): a whole-view mask of ones through the blend op has the bits of the schedulers' own given-view path.
+// The form is a * cond + s * noise with BOTH products rounded before the sum (three roundings): what the scheduler kernels have always
+// computed (one packed multiply and an add).  Under -ffp-contract=fast the compiler decides per call site whether a product is fused into
+// the sum — blend_kernel got mul + fma from the same expression, i.e. other bits — and a contract(off) pragma does not bind the backend's
+// fusion.  The empty asm makes the two products opaque values, so no site can fuse them.
+__device__ __forceinline__ float renoise_f(float a, float cond, float s, float noise) {
+    float pc = a * cond, pn = s * noise;
+    asm("" : "+v"(pc), "+v"(pn));
+    return pc + pn;
+}
+
 // x * sigmoid(x) with v_rcp_f32 (1 ulp) instead of the IEEE division sequence (v_div_scale / v_div_fmas / v_div_fixup: ~12 instructions)
 __device__ __forceinline__ float silu_f(float x) { return x * __frcp_rn(1.0f + __expf(-x)); }
 // erf GELU (attention.py:259-280 uses F.gelu's default, exact form): gelu(x) = 0.5 x (1 + erf(x / sqrt 2)).

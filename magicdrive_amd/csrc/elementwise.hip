@@ -435,7 +435,7 @@ __global__ __launch_bounds__(256) void ddim_kernel(DdimParams p) {
         float x = p.x[i];
         float x0 = (x - c[1] * e) / c[0];
         float xn = c[2] * x0 + c[3] * e;
-        if (given && p.gv_mode == 1 && step < p.gv_last) xn = c[2] * p.gv_cond[i] + c[3] * p.gv_noise[i];
+        if (given && p.gv_mode == 1 && step < p.gv_last) xn = renoise_f(c[2], p.gv_cond[i], c[3], p.gv_noise[i]);
         p.x[i] = xn;
         if (p.x_in) {
             if (p.xin_ld > 0) {          // bf16 channels-last copy with padded pixel stride
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(256) void unipc_kernel(UniPCParams p) {
     float xc = x;
     if (c[2] != 0.f) xc = c[3] * p.x_last[i] + c[4] * m1 + c[5] * m2 + c[6] * mt;
     float xn = c[7] * xc + c[8] * mt + c[9] * m1;
-    if (given && p.gv_mode == 1 && step < p.gv_last) xn = c[10] * p.gv_cond[i] + c[11] * p.gv_noise[i];
+    if (given && p.gv_mode == 1 && step < p.gv_last) xn = renoise_f(c[10], p.gv_cond[i], c[11], p.gv_noise[i]);
     p.x[i] = xn; p.x_last[i] = xc; p.m2[i] = m1; p.m1[i] = mt;
     if (p.x_in) {
         if (p.xin_ld > 0) {

@@ -298,7 +298,7 @@ class SamplerPlan:
 
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
-                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None):
+                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None, keep_regions: bool = False):
         """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
         1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
         from cond.live on the device.  Self and cross-view attention are untouched.
@@ -308,7 +308,12 @@ class SamplerPlan:
           None (default): nothing is emitted — prologue and step programs are op for op those of a plan built without the argument.
           "trace": ONE op appended to the step program, behind the scheduler step, row-selected by step_ctr: one record per step and view,
                    written inside the captured step graph (at which step did a view die?).
-          "final": no per-step op; run_health() launches one op over the final latents behind the loop."""
+          "final": no per-step op; run_health() launches one op over the final latents behind the loop.
+        keep_regions (with given_view_mode 1): the known views carry a per-pixel keep mask (self.keep, fp32 [b * n_cam, h, w] in [0, 1]: 1 keeps
+          the known latent, 0 regenerates, a fraction mixes).  The scheduler op is emitted with its given-view fields OFF and one
+          ops.LatentBlend follows it (in front of the health trace op, whose records then see the blended latents): after every step but
+          the last, x <- m * add_noise(cond, noise, t_next) + (1 - m) * x.  UniPC's history keeps the values computed from the un-blended
+          samples, as under gv_mode 1 (include/mdx.h).  False (default): prologue and step programs are op for op those of today."""
         self.cfg, self.device = cfg, device
         assert health in (None, "final", "trace"), f"health={health!r}: None, 'final' or 'trace'"
         self.health = health
@@ -318,6 +323,8 @@ class SamplerPlan:
         assert not dynamic_boxes or L_box > 0, "dynamic_boxes needs a box capacity >= 1 (calls without boxes keep their exact plan)"
         assert scheduler_kind in ("ddim", "unipc")
         assert given_view_mode in (0, 1, 2)
+        assert not keep_regions or given_view_mode == 1, "keep_regions is the per-pixel form of given_view_mode 1 (re-noised known latents)"
+        self.keep_regions = bool(keep_regions)
         self.scheduler_kind = scheduler_kind
         self.given_view_mode = given_view_mode
         n_cam = len(cfg["neighboring_view_pair"])
@@ -345,6 +352,8 @@ class SamplerPlan:
             self.gv_mask = torch.zeros(b * n_cam, dtype=torch.uint8, device=device)
             self.gv_cond = torch.zeros_like(self.x)
             self.gv_noise = torch.zeros_like(self.x)
+        if self.keep_regions:
+            self.keep = torch.zeros(b * n_cam, h, w, dtype=F32, device=device)         # one value per latent pixel (mask_elems = Cl)
         # ---------------- prologue ----------------
         self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text, dynamic=dynamic_boxes, cfg_halves=self.c)
         if self.dynamic_boxes:
@@ -405,18 +414,21 @@ class SamplerPlan:
         bld.free(y)
         if scheduler_kind == "ddim":
             gv = {}
-            if given_view_mode:
+            if given_view_mode and not self.keep_regions:
                 gv = dict(gv_mask=self.gv_mask, gv_cond=self.gv_cond.view(-1), gv_noise=self.gv_noise.view(-1), gv_mode=given_view_mode,
                           gv_last_step=num_steps - 1)
             bld.emit(O.DdimStep(self.x.view(-1), self.eps.view(-1), self.coef, self.step_ctr, x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg,
                                 guidance=guidance_scale, xin_c=Cl, name="cfg+ddim", **gv))
         else:
             gv = {}
-            if given_view_mode:
+            if given_view_mode and not self.keep_regions:
                 gv = dict(gv_mask=self.gv_mask, gv_cond=self.gv_cond.view(-1), gv_noise=self.gv_noise.view(-1), gv_mode=given_view_mode,
                           gv_last_step=num_steps - 1)
             bld.emit(O.UniPCStep(self.x.view(-1), self.eps.view(-1), self.coef, self.step_ctr, self.x_last.view(-1), self.m1.view(-1),
                                  self.m2.view(-1), x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, guidance=guidance_scale, xin_c=Cl, name="cfg+unipc", **gv))
+        if self.keep_regions:       # behind the scheduler op (which has advanced step_ctr), in front of the health trace op
+            bld.emit(O.LatentBlend(self.x.view(-1), self.gv_cond.view(-1), self.gv_noise.view(-1), self.keep.view(-1), self.coef, self.step_ctr,
+                                   last_step=num_steps - 1, x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, xin_c=Cl, name="keep_regions"))
         self._health = None
         self.health_ops: List = []
         if health == "trace":
@@ -500,9 +512,12 @@ class SamplerPlan:
 
     # ---- per-call inputs ----
     def load_inputs(self, latents: torch.Tensor, camera_param, text, bev_map, boxes, timesteps: torch.Tensor, coef: torch.Tensor,
-                    given_mask: Optional[torch.Tensor] = None, given_latents: Optional[torch.Tensor] = None):
+                    given_mask: Optional[torch.Tensor] = None, given_latents: Optional[torch.Tensor] = None,
+                    keep_mask: Optional[torch.Tensor] = None):
         """latents (b, n_cam, C, h, w) any float dtype; camera/text/map/boxes already hold the [uncond | cond] halves.
-        given_mask (b, n_cam) bool + given_latents (b, n_cam, C, h, w): the known views of a given-view plan."""
+        given_mask (b, n_cam) bool + given_latents (b, n_cam, C, h, w): the known views of a given-view plan.
+        keep_mask (b, n_cam, h, w) in [0, 1], a keep_regions plan only (validated by the caller; zero on views that are not given): the
+        first sample is m * add_noise(cond, noise, t_0) + (1 - m) * noise, with exact m == 1 / m == 0 taking the term itself."""
         b, nc = self.b, self.n_cam
         assert latents.shape[:2] == (b, nc)
         xl = latents.to(self.device, F32).reshape(b * nc, *latents.shape[2:]).permute(0, 2, 3, 1).contiguous()
@@ -517,9 +532,18 @@ class SamplerPlan:
                 a0, s0 = c0[0], c0[1]                                                # DDIM row: sqrt(acp_t), sqrt(1 - acp_t), ...
             else:
                 a0, s0 = 1.0 / c0[0], -c0[1] / c0[0]                                 # UniPC row: a = 1 / alpha_t, b = -sigma_t / alpha_t
-            xl = torch.where(gm.view(-1, 1, 1, 1), a0 * self.gv_cond + s0 * self.gv_noise, xl)
+            t0 = a0 * self.gv_cond + s0 * self.gv_noise
+            if self.keep_regions:
+                assert keep_mask is not None and tuple(keep_mask.shape) == (b, nc, self.h, self.w), "keep_mask must be (b, n_cam, h, w)"
+                self.keep.copy_(keep_mask.to(self.device, F32).reshape(b * nc, self.h, self.w))
+                m = self.keep.unsqueeze(-1)
+                xl = torch.where(m == 1, t0, torch.where(m == 0, xl, m * t0 + (1 - m) * xl))
+            else:
+                assert keep_mask is None, "this plan was built without keep_regions"
+                xl = torch.where(gm.view(-1, 1, 1, 1), t0, xl)
         else:
             assert given_mask is None, "this plan was built without given views"
+            assert keep_mask is None, "this plan was built without keep_regions"
         self.x.copy_(xl)
         self.x_in.view(self.c, b * nc, self.h, self.w, CIN_PAD)[..., :xl.shape[-1]].copy_(self.x.unsqueeze(0).expand(self.c, *self.x.shape))
         self.cond.load(camera_param, text, bev_map, boxes)

@@ -76,6 +76,9 @@ def op_bytes(op) -> float:
         return nb(op.Q) + nb(op.K) + nb(op.V) + nb(op.O)
     if isinstance(op, (O.GroupNorm, O.LayerNorm)):
         return nb(op.X) + nb(op.Y)
+    if isinstance(op, O.LatentBlend):
+        # 0 MFMA flops (op_flops), bytes only, every operand once: x read and written, cond, noise, the mask, the x_in copies
+        return 2 * nb(op.x) + nb(op.cond) + nb(op.noise) + nb(op.mask) + nb(op.x_in)
     if isinstance(op, (O.Ew, O.Upsample, O.Layout)):
         return nb(op.X) + nb(op.Y) * (2 if getattr(op, "kind", 0) == 1 else 1)
     return 0.0

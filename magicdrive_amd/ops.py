@@ -712,6 +712,59 @@ class Sdpa:
         return self.opcode, d
 
 
+@dataclass
+class LatentBlend:
+    """Keep known regions of the latents (MdxBlendDesc, csrc/blend.hip), placed BEHIND the scheduler op of a step: with s = step - 1 (the
+    scheduler op has advanced the counter) and s in [0, last_step), element i with m = mask[i // (n / mask.numel())] becomes
+    m == 0: untouched; m == 1: t = coef[s, col_a] * cond + coef[s, col_s] * noise; else fma(m, t - x, x) — and x_in is refreshed as the
+    scheduler ops do.  x, cond, noise fp32 [n] in one layout; mask fp32, one value per n / mask.numel() consecutive elements (per latent
+    pixel of an NHWC latent); coef / step / x_in / cfg / xin_c: the scheduler op's.  col_a / col_s: 2, 3 of a DDIM table, 10, 11 of UniPC's.
+    The build follows x_in's 16-bit type (dtype_code); with an fp32 x_in or none the two builds are the same kernel."""
+    x: torch.Tensor
+    cond: torch.Tensor
+    noise: torch.Tensor
+    mask: torch.Tensor
+    coef: torch.Tensor                   # fp32 [steps, 4 | 12]
+    step: torch.Tensor                   # int32 [1]
+    last_step: int
+    col_a: int = -1                      # -1: by the table's width (4 -> 2, 3; 12 -> 10, 11)
+    col_s: int = -1
+    x_in: Optional[torch.Tensor] = None
+    cfg: bool = False
+    xin_c: int = 0
+    name: str = ""
+    opcode = L.OP_LATENT_BLEND
+
+    COLUMNS = {4: (2, 3), 12: (10, 11)}  # (alpha, sigma) of the next timestep in a DDIM / UniPC coefficient row
+
+    def lower(self):
+        n = self.x.numel()
+        _chk(all(t.dtype == F32 and t.is_contiguous() and t.numel() == n for t in (self.x, self.cond, self.noise)), f"blend {self.name}: x, cond, noise must be fp32, dense, of one size")
+        _chk(self.mask.dtype == F32 and self.mask.is_contiguous() and self.mask.numel() > 0 and n % self.mask.numel() == 0,
+             f"blend {self.name}: mask must be fp32, dense, with a size dividing n={n}")
+        _chk(self.coef.dtype == F32 and self.coef.dim() == 2 and self.coef.is_contiguous() and self.step.dtype == torch.int32 and self.step.numel() == 1,
+             f"blend {self.name}: coef fp32 [steps, ld], step int32 [1]")
+        ld = self.coef.shape[1]
+        col_a, col_s = self.col_a, self.col_s
+        if col_a < 0 or col_s < 0:
+            _chk(ld in self.COLUMNS, f"blend {self.name}: a coefficient table of width {ld} needs col_a / col_s")
+            col_a, col_s = self.COLUMNS[ld]
+        _chk(0 <= col_a < ld and 0 <= col_s < ld, f"blend {self.name}: columns {col_a}, {col_s} of a table of width {ld}")
+        d = L.MdxBlendDesc()
+        d.x, d.cond, d.noise, d.mask, d.coef, d.step_ptr, d.x_in = _p(self.x), _p(self.cond), _p(self.noise), _p(self.mask), _p(self.coef), _p(self.step), _p(self.x_in)
+        c = 2 if self.cfg else 1
+        if self.x_in is not None:
+            if self.x_in.dtype == F32:
+                _chk(self.x_in.is_contiguous() and self.x_in.numel() == c * n, f"blend {self.name}: fp32 x_in must hold {c} x n elements")
+            else:
+                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.x_in.is_contiguous() and self.xin_c > 0, f"blend {self.name}: 16-bit x_in must be [pixels, ld]")
+                _chk(self.x_in.shape[0] * self.xin_c == c * n and self.x_in.shape[1] >= self.xin_c, f"blend {self.name}: 16-bit x_in shape")
+                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
+        d.n, d.mask_elems, d.coef_ld, d.col_a, d.col_s = n, n // self.mask.numel(), ld, col_a, col_s
+        d.last_step, d.cfg = int(self.last_step), int(self.cfg)
+        return self.opcode, d
+
+
 def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, scale: Optional[float] = None, causal: bool = False,
          key_lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(scale * q k^T + mask) v per head on the GPU kernel behind mdx_sdpa_* (ops.Sdpa), on torch's current stream.

@@ -122,6 +122,15 @@ class StableDiffusionBEVControlNetPipeline:
         # None: only non-finite values make a scene bad.  A float: a finite |latent| above it does too.  There is NO default threshold:
         # nobody has measured the latent range of trained weights on this path.
         self.health_absmax: Optional[float] = None
+        # Keep known REGIONS of given views (StableDiffusionBEVControlNetGivenViewPipeline only; an attribute because __call__ keeps the
+        # reference's signature).  None (default): today's path, plan key included.  Set: a B x N_cam list, each entry None or an (h, w)
+        # tensor in [0, 1] at latent resolution — 1 keeps the view's conditional latent at that latent pixel, 0 regenerates it, a fraction
+        # mixes (a box edge inside the 8x8 image pixels of a latent pixel).  None on a view WITH a conditional latent keeps the whole view;
+        # a view without one is regenerated and takes no mask.  After every step but the last the sample becomes
+        # m * add_noise(cond, noise, t_next) + (1 - m) * sample (ops.LatentBlend behind the scheduler op): the kept background of the
+        # result is the model's own last-step output given that context, NOT the encoded input; a pixel-space composite with the
+        # original pictures is left to the caller.  magicdrive_amd.dataset.regions.box_keep_mask builds the masks from projected boxes.
+        self.keep_masks: Optional[List[List[Optional[torch.Tensor]]]] = None
 
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
@@ -321,14 +330,49 @@ class StableDiffusionBEVControlNetPipeline:
         return (cap, "scene", (cap, "scene")) if scene else (cap, True, (cap, "dynamic"))
 
     def _plan_key(self, n_scene, chunk, do_cfg, box_key, h, w, n_steps, guidance_scale, conditioning_scale, n_text, sched_kind, gv_mode, pdt, fork,
-                  health=None):
+                  health=None, regions=False):
         """Cache key of one scene chunk's SamplerPlan.  `health` enters as a trailing entry only when it is on: with the switch off the key is,
-        entry for entry, what it was before the switch existed."""
+        entry for entry, what it was before the switch existed.  Likewise `regions` (pipe.keep_masks set): a trailing ("regions",)."""
         key = (n_scene, chunk, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(conditioning_scale), n_text, sched_kind,
                gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
         if health is not None:
             key = key + (("health", health),)
+        if regions:
+            key = key + (("regions",),)
         return key
+
+    def _checked_keep_masks(self, given_view, height: int, width: int) -> torch.Tensor:
+        """pipe.keep_masks as one (B, N_cam, h, w) fp32 tensor on the host: None on a view with a conditional latent -> ones, a view without
+        one -> zeros.  Every refusal is a ValueError raised here, before any device work of the call."""
+        masks = self.keep_masks
+        if given_view is None:
+            raise ValueError("keep_masks is set, but this pipeline has no given views: masks belong to the conditional_latents of "
+                             "StableDiffusionBEVControlNetGivenViewPipeline (set pipe.keep_masks = None for a plain call)")
+        cond_lat, every_input = given_view
+        if not every_input:
+            raise ValueError("keep_masks needs conditional_latents_change_every_input=True: a kept region is the known latent re-noised to "
+                             "every step's level; the False branch (noise-prediction override) has no per-pixel form")
+        h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        if len(masks) != len(cond_lat) or any(len(mr) != len(cr) for mr, cr in zip(masks, cond_lat)):
+            raise ValueError(f"keep_masks must be a B x N_cam list like conditional_latents: got {[len(r) for r in masks]} rows for "
+                             f"{[len(r) for r in cond_lat]}")
+        out = torch.zeros(len(cond_lat), max((len(r) for r in cond_lat), default=0), h, w, dtype=torch.float32)
+        for i, (mr, cr) in enumerate(zip(masks, cond_lat)):
+            for j, (m, v) in enumerate(zip(mr, cr)):
+                if m is None:
+                    if v is not None:
+                        out[i, j] = 1.0
+                    continue
+                if v is None:
+                    raise ValueError(f"keep_masks[{i}][{j}]: a mask on a view without a conditional latent (nothing is known there to keep)")
+                m = torch.as_tensor(m)
+                if tuple(m.shape) != (h, w):
+                    raise ValueError(f"keep_masks[{i}][{j}]: shape {tuple(m.shape)}, expected the latent size ({h}, {w})")
+                mf = m.detach().to("cpu", torch.float32)
+                if not bool(torch.isfinite(mf).all()) or float(mf.min()) < 0.0 or float(mf.max()) > 1.0:
+                    raise ValueError(f"keep_masks[{i}][{j}]: values must be finite and in [0, 1] (1 keeps, 0 regenerates)")
+                out[i, j] = mf
+        return out
 
     def _plan_config(self) -> Dict[str, Any]:
         """Architecture config of the sampler plan: the UNet's, with the conditioning encoders' geometry taken from the ControlNet."""
@@ -349,6 +393,9 @@ class StableDiffusionBEVControlNetPipeline:
                  bbox_max_length=None, _given_view=None):
         """`_given_view` = (conditional_latents, change_every_input) is how StableDiffusionBEVControlNetGivenViewPipeline reuses
         this body; not part of the reference signature."""
+        keep = None
+        if getattr(self, "keep_masks", None) is not None:      # refused or accepted on the host, before anything else of the call
+            keep = self._checked_keep_masks(_given_view, height, width)
         if guess_mode:
             # the reference's own guess path cannot run either: under CFG it feeds the ControlNet 5-D `latents` with a 2x-batched camera_param
             # and the un-repeated prompt (pipeline_bev_controlnet.py:366-373) — refused rather than guessed at
@@ -460,7 +507,7 @@ class StableDiffusionBEVControlNetPipeline:
             # built on the old PackedNet would keep running (and keep alive) the old ones
             # box_bucket: the key carries (capacity, "dynamic") in the place of L_box, scene_boxes (capacity, "scene"); neither / no boxes: today's key
             key = self._plan_key(s1 - s0, ci, do_cfg, box_key, h, w, n_steps, guidance_scale, controlnet_conditioning_scale, text.shape[1], sched_kind,
-                                 gv_mode, pdt, fork, health)
+                                 gv_mode, pdt, fork, health, regions=keep is not None)
             plan = self._plans.get(key)
             if plan is None:
                 with torch.cuda.device(device):
@@ -471,13 +518,14 @@ class StableDiffusionBEVControlNetPipeline:
                     plan = SamplerPlan(plan_cfg, self.unet.packed(), self.controlnet.packed(), device, s1 - s0, do_cfg, L_plan, (h, w),
                                        num_steps=n_steps, guidance_scale=guidance_scale,
                                        conditioning_scale=float(controlnet_conditioning_scale), n_text=text.shape[1], scheduler_kind=sched_kind,
-                                       given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes, **({} if health is None else {"health": health}))
+                                       given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes, **({} if health is None else {"health": health}),
+                                       **({} if keep is None else {"keep_regions": True}))
                     plan.compile()
                 self._plans.put(key, plan)
             plan.load_inputs(latents[s0:s1], rows(camera_param, s0, s1), rows(text, s0, s1), rows(image, s0, s1),
                              None if boxes is None else {k: rows(v, s0, s1) for k, v in boxes.items()}, timesteps,
                              self.scheduler.coefficient_table(), given_mask=None if gv_mask is None else gv_mask[s0:s1],
-                             given_latents=None if gv_lat is None else gv_lat[s0:s1])
+                             given_latents=None if gv_lat is None else gv_lat[s0:s1], **({} if keep is None else {"keep_mask": keep[s0:s1]}))
             plans.append(plan)
         with torch.cuda.device(device):                       # launches, graph replays and torch copies all target the pipeline's device
             main = torch.cuda.current_stream(device)

@@ -4,6 +4,10 @@ Same sampler as StableDiffusionBEVControlNetPipeline with some views' clean late
 B x N_cam list of (C, h, w) tensors or None).  The reference re-noises the known views on the host at the top of every
 iteration (:280-291, `conditional_latents_change_every_input=True`) or overrides their noise prediction (:380-390, False);
 here both are branches of the fused CFG + DDIM kernel (MdxDdimDesc.gv_*), so the loop stays one hipGraph replay per step.
+
+`pipe.keep_masks` (an attribute: the call signature is the reference's; default None = everything above, unchanged) keeps REGIONS of the
+known views: a B x N_cam list of None or (h, w) tensors in [0, 1] — the per-pixel, fractional form of the change_every_input=True
+branch, one ops.LatentBlend behind the scheduler op (StableDiffusionBEVControlNetPipeline.__init__ documents it).
 """
 from __future__ import annotations
 

@@ -5,11 +5,18 @@ load a checkpoint in the reference layout, read the training run's hydra overrid
 
   python tools/sample.py --ckpt <ckpt dir with unet/ controlnet/ hydra/overrides.yaml> --sd15 <stable-diffusion-v1-5 dir> \
          --data <folder of *.pth> --out <dir> [key=value overrides as for tools/test.py] [--scheduler unipc|ddim] [--prompt-embeds]
-         [--cond-on-view]
+         [--cond-on-view] [--regenerate-boxes [--region-dilate N]]
 
 --cond-on-view is demo/run_cond_on_view.py:34-120: the pipe class becomes StableDiffusionBEVControlNetGivenViewPipeline, the ground-truth
 views of every sample (`img` of the `.pth`) are encoded with the pipeline's VAE (`vae.encode(x).latent_dist.mean * scaling_factor`, on
 the HIP kernels), and generation `ti` of the `validation_times - 1` generations is sampled with view `ti` given.
+
+--regenerate-boxes is box editing on recorded scenes (the use demo/interactive_gui.py and demo/run_cond_on_view.py serve): the inputs of
+--cond-on-view, but ALL ground-truth views are encoded and given, and `pipe.keep_masks` — one (h, w) mask per view from the sample's own
+boxes (magicdrive_amd.dataset.box_keep_mask: 1 - coverage of each latent pixel by the projected boxes, grown by --region-dilate latent
+pixels, default 1) — lets the sampler regenerate the boxes and keep everything else.  `validation_times` generations, one pipe() call each,
+seeded as the plain loop is (there is no "view ti given" rule), the same files and index.json.  The kept background is the model's own
+last-step output given the known latents, not the encoded input; compositing with the original pictures is left to the caller.
 
 No hydra / omegaconf / mmdet3d: the config tree of the reference is not rebuilt (SURVEY.md §8 out of scope) — only the handful of
 keys the sampling loop reads are resolved, in the reference's order (checkpoint overrides first, command line last, tools/test.py:46-54):
@@ -97,9 +104,10 @@ def iter_batches_index(n: int, batch_size: int) -> Iterator[List[int]]:
         yield list(range(i0, min(i0 + batch_size, n)))
 
 
-def iter_pipe_kwargs(dataset, run: Dict, batch_size: int = 1, with_pixels: bool = False, only=None) -> Iterator[Dict]:
+def iter_pipe_kwargs(dataset, run: Dict, batch_size: int = 1, with_pixels: bool = False, only=None, with_meta: bool = False) -> Iterator[Dict]:
     """Batches of samples -> keyword arguments of StableDiffusionBEVControlNetPipeline.__call__, as run_one_batch /
-    run_one_batch_pipe assemble them (magicdrive/misc/test_utils.py:191-255, :258-330).  with_pixels: (kwargs, pixel_values) pairs.
+    run_one_batch_pipe assemble them (magicdrive/misc/test_utils.py:191-255, :258-330).  with_pixels: (kwargs, pixel_values) pairs;
+    with_meta: (kwargs, pixel_values, meta_data) triples (the samples' boxes and camera matrices, one list entry per scene).
     only: the batch indices to produce (a rank's share: rank_batches)."""
     from magicdrive_amd.dataset import collate_samples, preprocess_fn
     extra = {k: v for k, v in run.items() if k not in DEFAULTS or k in ("guidance_scale", "num_inference_steps")}
@@ -110,7 +118,9 @@ def iter_pipe_kwargs(dataset, run: Dict, batch_size: int = 1, with_pixels: bool 
         kw = dict(prompt=batch["captions"], image=batch["bev_map_with_aux"], camera_param=batch["camera_param"],
                   height=run["image_size"][0], width=run["image_size"][1], bev_controlnet_kwargs=batch["kwargs"],
                   bbox_max_length=run["bbox_max_length"], **extra)
-        if with_pixels:
+        if with_meta:
+            yield kw, batch["pixel_values"], batch["meta_data"]
+        elif with_pixels:
             yield kw, batch["pixel_values"]
         else:
             yield kw
@@ -141,6 +151,24 @@ def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, gen
             generator = torch.Generator().manual_seed(run["seed"])         # :97-99
         out = pipe(conditional_latents=conditional_latents, generator=generator, **kw)
         yield ti, (out if full_output else out.images)
+
+
+def regenerate_boxes_inputs(pipe, pixel_values: torch.Tensor, meta: Dict, run: Dict, dilate: int = 1) -> Dict:
+    """--regenerate-boxes, per batch: every ground-truth view encoded (encode_given_views) and given, and pipe.keep_masks set from each
+    sample's own boxes — project_box_corners with the sample's lidar2image / img_aug_matrix, box_keep_mask at the run's image size and the
+    latents' (h, w).  Returns the extra keyword arguments of the batch's pipe() calls: {conditional_latents}."""
+    from magicdrive_amd.dataset import box_keep_mask, project_box_corners
+    if pixel_values is None:
+        raise ValueError("--regenerate-boxes needs the ground-truth views (`img`) in the samples")
+    latents = encode_given_views(pipe, pixel_values)
+    bs, n_cam = latents.shape[:2]
+    masks = []
+    for boxes, l2i, aug in zip(meta["gt_bboxes_3d"], meta["lidar2image"], meta["img_aug_matrix"]):
+        corners, kept = project_box_corners(boxes, l2i, aug)
+        masks.append(list(box_keep_mask(corners, kept, tuple(run["image_size"]), tuple(latents.shape[-2:]), dilate=dilate)))
+    assert len(masks) == bs and all(len(m) == n_cam for m in masks)
+    pipe.keep_masks = masks
+    return dict(conditional_latents=[[latents[b, v] for v in range(n_cam)] for b in range(bs)])
 
 
 def build_pipe(ckpt: str, sd15: str, scheduler: str, device, given_view: bool = False, hip_text_encoder: bool = False):
@@ -270,6 +298,9 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default=None, help="torch.distributed backend under torchrun (default: nccl = RCCL with a GPU, else gloo)")
     ap.add_argument("--reseed-per-run", action="store_true", help="deviation from the reference: an independent seed per (batch, validation run)")
     ap.add_argument("--cond-on-view", action="store_true", help="demo/run_cond_on_view.py: generation ti is sampled with the encoded ground-truth view ti given")
+    ap.add_argument("--regenerate-boxes", action="store_true", help="box editing: all ground-truth views are encoded and given, pipe.keep_masks keeps every latent "
+                    "pixel outside the sample's projected boxes (INTEGRATION.md §1); validation_times generations, seeded as the plain loop")
+    ap.add_argument("--region-dilate", type=int, default=1, help="--regenerate-boxes: grow the regenerated region by N latent pixels (default 1)")
     ap.add_argument("--box-bucket", type=int, default=None, help="one sampler plan per bucket of N padded box counts (pipe.box_bucket, INTEGRATION.md §1): the "
                     "padded box count changes with almost every batch of a validation run; default: an exact plan per count")
     ap.add_argument("--scene-boxes", action="store_true", help="every scene of a batch attends to its own boxes only (pipe.scene_boxes, INTEGRATION.md §1): "
@@ -286,12 +317,17 @@ def main(argv=None):
     rank, world, local = DD.init_from_env(backend=a.dist_backend)
     device = a.device or (f"cuda:{local}" if torch.cuda.is_available() else "cpu")
     run = resolve_run_config(a.ckpt, a.overrides)
+    if a.regenerate_boxes and a.cond_on_view:
+        raise SystemExit("--regenerate-boxes gives every view with a mask; --cond-on-view gives view ti whole: pass one of the two")
+    if a.region_dilate < 0:
+        raise SystemExit("--region-dilate must be >= 0")
+    given_view = a.cond_on_view or a.regenerate_boxes
     if a.pipe_factory:
         import importlib
         mod, fn = a.pipe_factory.split(":")
-        pipe = getattr(importlib.import_module(mod), fn)(a.ckpt, a.sd15, a.scheduler, device, a.cond_on_view)
+        pipe = getattr(importlib.import_module(mod), fn)(a.ckpt, a.sd15, a.scheduler, device, given_view)
     else:
-        pipe = build_pipe(a.ckpt, a.sd15, a.scheduler, device, given_view=a.cond_on_view, hip_text_encoder=a.hip_text_encoder)
+        pipe = build_pipe(a.ckpt, a.sd15, a.scheduler, device, given_view=given_view, hip_text_encoder=a.hip_text_encoder)
     if a.box_bucket is not None:
         if a.box_bucket < 1:
             raise SystemExit("--box-bucket must be >= 1")
@@ -313,13 +349,13 @@ def main(argv=None):
     index: List[Dict] = []
     n_local = 0
     n_bad_local = 0
-    it = iter_pipe_kwargs(data, run, a.batch_size, with_pixels=a.cond_on_view, only=mine)
+    it = iter_pipe_kwargs(data, run, a.batch_size, with_pixels=a.cond_on_view, only=mine, with_meta=a.regenerate_boxes)
     for rnd in range(n_rounds):
         j = rnd * world + rank
         records, images_out = [], []
         if j < len(batches):
             item = next(it)
-            kw, pixel_values = item if a.cond_on_view else (item, None)
+            kw, pixel_values, meta = item if a.regenerate_boxes else ((*item, None) if a.cond_on_view else (item, None, None))
             bs = kw["image"].shape[0]
             scene0 = batches[j][0]
             if getattr(pipe, "text_encoder", None) is None:
@@ -339,6 +375,8 @@ def main(argv=None):
                         records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed, **(health_fields(out.health, bi) if health_on else {})))
                         images_out.append(views)
             else:
+                if a.regenerate_boxes:                  # every view given, masked by the sample's boxes; the loop below is the plain one
+                    kw = dict(kw, **regenerate_boxes_inputs(pipe, pixel_values, meta, run, a.region_dilate))
                 for ti in range(run["validation_times"]):
                     g = gen
                     if a.reseed_per_run and base_gen is not None:
