@@ -559,6 +559,48 @@ typedef struct MdxBlendDesc {
 } MdxBlendDesc;
 int mdx_latent_blend_bf16(const MdxBlendDesc* d, void* stream);
 
+/*
+ * mdx_latent_renoise_bf16 / _f16 — one forward jump of the sampler with Gaussian noise made on the device: the resampling move of RePaint
+ * (Lugmayr et al. 2022; scheduling_repaint.py undo_step, `jump` of them in one go), for kept-region edits (additive symbols, the ABI
+ * version stays 12; MDX_OP_LATENT_RENOISE; csrc/noise.hip; mdx_last_kernel() starts with "renoise_kernel").  An op of its own, launched
+ * BETWEEN steps; no scheduler or blend descriptor changes.  The two builds differ only in the 16-bit type of x_in.
+ *   x         : fp32 [n] latents, updated in place;   x_in : the model-input copies, as in MdxBlendDesc (may be NULL);
+ *   coef      : the scheduler's table, n_rows rows of coef_ld floats;
+ *   step_ptr  : int32, the scheduler op's counter, READ AND WRITTEN;   visit_ptr : int32 jump counter, READ AND WRITTEN;
+ *   seeds     : uint64 [n / group_elems], device memory: one seed per group of group_elems consecutive elements (a view).
+ * With c = *step_ptr and v = *visit_ptr, both read when the kernel RUNS (a replayed hipGraph sees the current values):
+ *   current level: the sample is where the scheduler op of step c - 1 left it, sqrt(abar) = coef[(c - 1) * coef_ld + col_p] (DDIM row: col_p = 2);
+ *   target level : the one step c - jump expects, coef[(c - jump) * coef_ld + col_t] (DDIM row: col_t = 0);
+ *   r = target / current, sg = sqrtf(fmaxf(0, 1 - r * r)) (fp32; 1 - r * r is fmaf(-r, r, 1): one rounding), and for every i < n:
+ *   x[i] = fmaf(r, x[i], sg * z[i]) with the product sg * z[i] rounded
+ * — q(x_{t+jump} | x_t), the distribution of `jump` single undo steps.  Every written element refreshes x_in as the scheduler kernels do:
+ * xin_ld == 0: fp32, flat; xin_ld > 0: the build's 16-bit type, channels-last with pixel stride xin_ld (pad channels never written);
+ * cfg != 0: both [uncond | cond] halves.  Then a separate one-thread launch (every block of the first has read the counters by then)
+ * sets *step_ptr = c - jump and *visit_ptr = v + 1.
+ * Out of range — jump < 1, c < 1, c > n_rows or c - jump < 0 — is a caller error discovered on the device: x is filled with NaN (the
+ * library's signal, as for a DDIM step index of -1), x_in and both counters are left alone.
+ * The noise z, to the bit of its inputs: element i belongs to group g = i / group_elems with relative index e = i - g * group_elems.
+ * One Philox4x32-10 call (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85) with counter
+ * (lo32(e / 4), hi32(e / 4), v, 0) and key (lo32(seeds[g]), hi32(seeds[g])) yields (w0, w1, w2, w3) for four consecutive e.
+ * u1(w) = ((w >> 8) + 1) * 2^-24 in (0, 1], u2(w) = (w >> 8) * 2^-24 in [0, 1), both exact in fp32.
+ * z[4k + 0] = sqrt(-2 ln u1(w0)) * cos(2 pi u2(w1)), z[4k + 1] the same radius with sin; z[4k + 2], z[4k + 3] from (w2, w3) likewise
+ * (fp32 evaluation, within 1e-5 of the exact value).  Group g's noise depends on seeds[g], v and e only: not on n, not on the group's
+ * position, not on the instance that served the call.
+ * fp32 math, no atomics, 64-bit addressing.  16-byte accesses when x is 16-byte aligned and group_elems % 4 == 0; any other case is
+ * SERVED by scalar accesses with the same bits.  Nothing is read or written past n elements, n / group_elems seeds, or the x_in pixels
+ * of n / xin_c rows (twice that many rows when cfg != 0).
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): x, coef, step_ptr, visit_ptr, seeds not
+ * NULL (x_in may be NULL); x, coef, step_ptr, visit_ptr 4-byte aligned, seeds 8-byte aligned, x_in at its element's alignment
+ * (4 / 2 bytes); n not negative; group_elems >= 1 and divides n; jump and n_rows fit a 32-bit int and are >= 1; 0 <= col_t, col_p <
+ * coef_ld; cfg in {0, 1}; xin_c, xin_ld, coef_ld fit a 32-bit int and xin_ld is not negative; xin_ld > 0 needs 0 < xin_c <= xin_ld and
+ * xin_c dividing n.  n == 0: MDX_OK (after the checks), nothing is launched.
+ */
+typedef struct MdxRenoiseDesc {
+    float* x; void* x_in; const float* coef; int32_t* step_ptr; int32_t* visit_ptr; const uint64_t* seeds;
+    int64_t n, group_elems, jump, n_rows, coef_ld, col_t, col_p, cfg, xin_c, xin_ld;
+} MdxRenoiseDesc;
+int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream);
+
 /* ---- program = array of ops, executed in order on one stream ------------ */
 #define MDX_OP_GEMM 1
 #define MDX_OP_CONV 2
@@ -578,6 +620,7 @@ int mdx_latent_blend_bf16(const MdxBlendDesc* d, void* stream);
 #define MDX_OP_GROUP_STATS 16          /* MdxStatsDesc through mdx_group_stats_* */
 #define MDX_OP_SDPA 17                 /* MdxSdpaDesc through mdx_sdpa_* */
 #define MDX_OP_LATENT_BLEND 18         /* MdxBlendDesc through mdx_latent_blend_* */
+#define MDX_OP_LATENT_RENOISE 19       /* MdxRenoiseDesc through mdx_latent_renoise_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -612,6 +655,7 @@ int mdx_attention_ctx_rows_f16(const MdxAttnDesc* d, void* stream);
 int mdx_group_stats_f16(const MdxStatsDesc* d, void* stream);
 int mdx_sdpa_f16(const MdxSdpaDesc* d, void* stream);
 int mdx_latent_blend_f16(const MdxBlendDesc* d, void* stream);
+int mdx_latent_renoise_f16(const MdxRenoiseDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

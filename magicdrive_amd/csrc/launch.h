@@ -25,6 +25,7 @@
 #define mdx_group_stats_bf16 mdx_group_stats_f16
 #define mdx_sdpa_bf16 mdx_sdpa_f16
 #define mdx_latent_blend_bf16 mdx_latent_blend_f16
+#define mdx_latent_renoise_bf16 mdx_latent_renoise_f16
 #endif
 // mdx_attention_* itself is defined in attention_short.hip (ABI 12): it checks the causal / v_rowmajor fields, serves the short-sequence
 // kernel and passes every other descriptor on to the flash kernels' entry point.  That one stays where it was, in attention.hip, which

@@ -1,0 +1,174 @@
+// noise.hip — mdx_latent_renoise_*: one forward jump of the sampler with noise made on the device (MdxRenoiseDesc, include/mdx.h).
+//
+// RePaint resampling (Lugmayr et al. 2022) diffuses the sample forward again by `jump` steps with fresh noise and takes the same reverse
+// steps once more.  With c = *step_ptr and v = *visit_ptr, read when the kernel runs (a replayed hipGraph sees the current values):
+//     current = coef[c - 1][col_p]          the level the scheduler op of step c - 1 left the sample at
+//     target  = coef[c - jump][col_t]       the level step c - jump expects
+//     r = target / current, sg = sqrt(max(0, fma(-r, r, 1))), x[i] = fma(r, x[i], sg z[i])    q(x_{t+jump} | x_t) in one go
+// and a separate one-thread launch behind it (the step_inc_kernel pattern of elementwise.hip: every block of the main launch has read
+// the counters by then) sets *step_ptr = c - jump, *visit_ptr = v + 1.  jump < 1, c < 1, c > n_rows or c - jump < 0: x is filled with
+// NaN (the library's signal, as ddim_kernel's for a step index of -1) and neither counter changes.
+//
+// z is a pure function of (seeds[g], v, e) for element e of group g = i / group_elems: Philox4x32-10 with counter
+// (lo32(e / 4), hi32(e / 4), v, 0) and key (lo32(seed), hi32(seed)) gives four words for four consecutive e; Box-Muller on (w0, w1) gives
+// z[4k], z[4k + 1], on (w2, w3) z[4k + 2], z[4k + 3] (include/mdx.h spells the mapping out).  Nothing depends on n, on the group's
+// position or on the instance that served the call: no generator state lives in memory, so a scene has the same noise alone and in a batch.
+//
+// Two instances of one body, one thread per block of four e: VEC moves the four with one 16-byte access (the launcher asks for a
+// 16-byte-aligned x and group_elems % 4 == 0, so every block is whole and aligned); the other moves 1 .. 4 elements one by one (the last
+// block of a group whose size is no multiple of four is partial).  Per element the arithmetic is the same function: same bits.  x_in is
+// refreshed element by element as the scheduler kernels do.  No atomics, 64-bit addressing.  The transcendentals are the accurate ones
+// (logf, sqrtf, sincospif on the EXACT argument 2 u2): |z - fp64| stays below 1e-5 up to the largest radius sqrt(48 ln 2).
+#include "common.h"
+#include "launch.h"
+
+namespace mdx {
+
+#define RN_T 256
+
+struct RenoiseParams { float* x; void* x_in; const float* coef; int* step; int* visit; const unsigned long long* seeds;
+                       long n, group, bpg; int jump, n_rows, coef_ld, col_t, col_p, cfg, xin_c, xin_ld; };
+
+__device__ __forceinline__ bool renoise_in_range(int c, int jump, int n_rows) { return jump >= 1 && c >= 1 && c <= n_rows && c - jump >= 0; }
+
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
+#pragma unroll
+    for (int round = 0; round < 10; ++round) {
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24 in [0, 1), both exact; (za, zb) = sqrt(-2 ln u1) (cos, sin)(2 pi u2)
+__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& za, float& zb) {
+    const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f, u2 = (float)(wb >> 8) * 0x1p-24f;
+    const float rad = sqrtf(-2.0f * logf(u1));
+    float sn, cs;
+    sincospif(2.0f * u2, &sn, &cs);
+    za = rad * cs; zb = rad * sn;
+}
+
+__device__ __forceinline__ float renoise_value(float r, float sg, float x, float z) {
+    float nz = sg * z;
+    asm("" : "+v"(nz));                                        // a rounded product in both instances, never folded into the fma below
+    return __builtin_fmaf(r, x, nz);
+}
+
+// the model-input copies of element i, exactly as ddim_kernel / unipc_kernel / blend_kernel write them
+__device__ __forceinline__ void renoise_xin(const RenoiseParams& p, long i, float v) {
+    if (!p.x_in) return;
+    if (p.xin_ld > 0) {
+        const long px = i / p.xin_c;
+        const int ch = (int)(i - px * p.xin_c);
+        bf16_t* xi = (bf16_t*)p.x_in;
+        const bf16_t h = f2bf(v);
+        xi[px * p.xin_ld + ch] = h;
+        if (p.cfg) xi[(p.n / p.xin_c + px) * p.xin_ld + ch] = h;
+    } else {
+        float* xi = (float*)p.x_in;
+        xi[i] = v;
+        if (p.cfg) xi[p.n + i] = v;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RN_T) void renoise_kernel(RenoiseParams p) {
+    const int c = *p.step, v = *p.visit;
+    const long q = (long)blockIdx.x * RN_T + threadIdx.x;       // block of four relative indices: group g, block k of the group
+    const long g = q / p.bpg;
+    if (g >= p.n / p.group) return;
+    const long k = q - g * p.bpg;
+    const long e0 = 4 * k;
+    const long i0 = g * p.group + e0;
+    const int cnt = VEC ? 4 : (int)(p.group - e0 < 4 ? p.group - e0 : 4);       // VEC: group % 4 == 0, every block is whole
+    if (!renoise_in_range(c, p.jump, p.n_rows)) {                // uniform over the launch: poison x, touch nothing else
+        for (int j = 0; j < cnt; ++j) p.x[i0 + j] = __builtin_nanf("");
+        return;
+    }
+    const float cur = p.coef[(long)(c - 1) * p.coef_ld + p.col_p], tgt = p.coef[(long)(c - p.jump) * p.coef_ld + p.col_t];
+    const float r = tgt / cur;
+    const float sg = sqrtf(fmaxf(0.0f, __builtin_fmaf(-r, r, 1.0f)));    // 1 - r r with ONE rounding, pinned (it cancels when r is near 1)
+    const unsigned long long seed = p.seeds[g];
+    unsigned w[4];
+    philox4x32_10((unsigned)(unsigned long long)k, (unsigned)((unsigned long long)k >> 32), (unsigned)v, 0u, (unsigned)seed, (unsigned)(seed >> 32), w);
+    float z[4];
+    box_muller(w[0], w[1], z[0], z[1]);
+    box_muller(w[2], w[3], z[2], z[3]);
+    if (VEC) {
+        const float4 x = *reinterpret_cast<const float4*>(p.x + i0);
+        float4 y;
+        y.x = renoise_value(r, sg, x.x, z[0]);
+        y.y = renoise_value(r, sg, x.y, z[1]);
+        y.z = renoise_value(r, sg, x.z, z[2]);
+        y.w = renoise_value(r, sg, x.w, z[3]);
+        *reinterpret_cast<float4*>(p.x + i0) = y;
+        renoise_xin(p, i0, y.x); renoise_xin(p, i0 + 1, y.y); renoise_xin(p, i0 + 2, y.z); renoise_xin(p, i0 + 3, y.w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < cnt) {
+                const float y = renoise_value(r, sg, p.x[i0 + j], z[j]);
+                p.x[i0 + j] = y;
+                renoise_xin(p, i0 + j, y);
+            }
+        }
+    }
+}
+
+// behind renoise_kernel on the same stream: the counters move only when the jump was taken
+__global__ void renoise_counters_kernel(int* step, int* visit, int jump, int n_rows) {
+    const int c = *step;
+    if (!renoise_in_range(c, jump, n_rows)) return;
+    *step = c - jump;
+    *visit += 1;
+}
+
+}  // namespace mdx
+
+using namespace mdx;
+
+extern "C" int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream) {
+#if MDX_F16
+    const char* op = "mdx_latent_renoise_f16";
+#else
+    const char* op = "mdx_latent_renoise";
+#endif
+    if (!d) return set_error(MDX_EINVAL, "%s: null descriptor", op);
+    if (!d->x) return set_error(MDX_EINVAL, "%s: x must not be NULL", op);
+    if (!d->coef) return set_error(MDX_EINVAL, "%s: coef must not be NULL", op);
+    if (!d->step_ptr) return set_error(MDX_EINVAL, "%s: step_ptr must not be NULL", op);
+    if (!d->visit_ptr) return set_error(MDX_EINVAL, "%s: visit_ptr must not be NULL", op);
+    if (!d->seeds) return set_error(MDX_EINVAL, "%s: seeds must not be NULL", op);
+    MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4)); MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4));
+    MDX_NEED(need_aligned(op, "visit_ptr", d->visit_ptr, 4)); MDX_NEED(need_aligned(op, "seeds", d->seeds, 8));
+    MDX_NEED(need_int(op, "xin_c", d->xin_c)); MDX_NEED(need_int(op, "xin_ld", d->xin_ld)); MDX_NEED(need_int(op, "coef_ld", d->coef_ld));
+    MDX_NEED(need_int(op, "jump", d->jump)); MDX_NEED(need_int(op, "n_rows", d->n_rows));
+    if (d->xin_ld < 0) return set_error(MDX_EINVAL, "%s: xin_ld=%ld must not be negative", op, (long)d->xin_ld);
+    MDX_NEED(need_aligned(op, "x_in", d->x_in, d->xin_ld > 0 ? 2 : 4));
+    if (d->n < 0) return set_error(MDX_EINVAL, "%s: n=%ld must not be negative", op, (long)d->n);
+    if (d->group_elems < 1 || d->n % d->group_elems) return set_error(MDX_EINVAL, "%s: group_elems=%ld must be >= 1 and divide n=%ld", op, (long)d->group_elems, (long)d->n);
+    if (d->jump < 1) return set_error(MDX_EINVAL, "%s: jump=%ld must be >= 1", op, (long)d->jump);
+    if (d->n_rows < 1) return set_error(MDX_EINVAL, "%s: n_rows=%ld must be >= 1", op, (long)d->n_rows);
+    if (d->col_t < 0 || d->col_t >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_t=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_t, (long)d->coef_ld);
+    if (d->col_p < 0 || d->col_p >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_p=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_p, (long)d->coef_ld);
+    if (d->cfg != 0 && d->cfg != 1) return set_error(MDX_EINVAL, "%s: cfg=%ld must be 0 or 1", op, (long)d->cfg);
+    if (d->xin_ld > 0 && (d->xin_c <= 0 || d->xin_c > d->xin_ld || d->n % d->xin_c))
+        return set_error(MDX_EINVAL, "%s: xin_c=%ld must be in (0, xin_ld=%ld] and divide n=%ld", op, (long)d->xin_c, (long)d->xin_ld, (long)d->n);
+    if (d->n == 0) return MDX_OK;
+    const long bpg = (long)((d->group_elems + 3) / 4);           // blocks of four relative indices per group; the last may be partial
+    RenoiseParams p{d->x, d->x_in, d->coef, d->step_ptr, d->visit_ptr, (const unsigned long long*)d->seeds, d->n, d->group_elems, bpg,
+                    (int)d->jump, (int)d->n_rows, (int)d->coef_ld, (int)d->col_t, (int)d->col_p, (int)d->cfg, (int)d->xin_c, (int)d->xin_ld};
+    const bool vec = ((uintptr_t)d->x & 15) == 0 && d->group_elems % 4 == 0;
+    const long work = (p.n / p.group) * bpg;
+    const long blocks = (work + RN_T - 1) / RN_T;
+    if (blocks > 0x7fffffffL) return set_error(MDX_EINVAL, "%s: n=%ld needs more than 2^31 - 1 workgroups", op, (long)d->n);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL((renoise_kernel<true>), dim3((unsigned)blocks), dim3(RN_T), 0, st, p);
+    else hipLaunchKernelGGL((renoise_kernel<false>), dim3((unsigned)blocks), dim3(RN_T), 0, st, p);
+    MDX_NEED(check_launch(vec ? "renoise_kernel" : "renoise_kernel_scalar"));
+    hipLaunchKernelGGL(renoise_counters_kernel, dim3(1), dim3(1), 0, st, p.step, p.visit, p.jump, p.n_rows);
+    return check_launch("renoise_counters_kernel", false);
+}

@@ -298,7 +298,8 @@ class SamplerPlan:
 
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
-                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None, keep_regions: bool = False):
+                 scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None, keep_regions: bool = False,
+                 resample: Optional[int] = None):
         """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
         1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
         from cond.live on the device.  Self and cross-view attention are untouched.
@@ -313,7 +314,13 @@ class SamplerPlan:
           the known latent, 0 regenerates, a fraction mixes).  The scheduler op is emitted with its given-view fields OFF and one
           ops.LatentBlend follows it (in front of the health trace op, whose records then see the blended latents): after every step but
           the last, x <- m * add_noise(cond, noise, t_next) + (1 - m) * x.  UniPC's history keeps the values computed from the un-blended
-          samples, as under gv_mode 1 (include/mdx.h).  False (default): prologue and step programs are op for op those of today."""
+          samples, as under gv_mode 1 (include/mdx.h).  False (default): prologue and step programs are op for op those of today.
+        resample (a jump length >= 1; with keep_regions and scheduler_kind "ddim" only): RePaint resampling.  The plan owns visit_ctr (int32 [1],
+          jumps taken in this call), seeds (int64 [b * n_cam], one per view) and ONE more program, self.jump = [ops.LatentRenoise]: x is
+          diffused forward again by `resample` steps with noise made on the device, step_ctr moves back by as many (time embeddings,
+          scheduler row, blend and health trace all select by it), visit_ctr moves on.  The caller launches it between steps
+          (schedulers.resample_actions; launch_jump).  The step program is unchanged, op for op.  UniPC is refused: its multistep history
+          (x_last, m1, m2) belongs to the trajectory a jump abandons.  None (default): nothing is allocated or built."""
         self.cfg, self.device = cfg, device
         assert health in (None, "final", "trace"), f"health={health!r}: None, 'final' or 'trace'"
         self.health = health
@@ -325,6 +332,10 @@ class SamplerPlan:
         assert given_view_mode in (0, 1, 2)
         assert not keep_regions or given_view_mode == 1, "keep_regions is the per-pixel form of given_view_mode 1 (re-noised known latents)"
         self.keep_regions = bool(keep_regions)
+        assert resample is None or (isinstance(resample, int) and not isinstance(resample, bool) and resample >= 1), f"resample={resample!r}: None or a jump length >= 1"
+        assert resample is None or keep_regions, "resample harmonises a kept-region edit: it needs keep_regions"
+        assert resample is None or scheduler_kind == "ddim", "resample is DDIM-only: UniPC's multistep history does not survive a jump"
+        self.resample = resample
         self.scheduler_kind = scheduler_kind
         self.given_view_mode = given_view_mode
         n_cam = len(cfg["neighboring_view_pair"])
@@ -441,6 +452,13 @@ class SamplerPlan:
             self.health_ops = [O.GroupStats(self.x.view(b * n_cam, -1), self._health, name="health.final")]
         self.step_ops = bld.ops
         bld.ops = []
+        self.jump_ops: List = []
+        self.jump: Optional[L.Program] = None
+        if resample is not None:    # a program of its own, launched between steps: one group (one seed) per view
+            self.visit_ctr = torch.zeros(1, dtype=torch.int32, device=device)
+            self.seeds = torch.zeros(b * n_cam, dtype=torch.int64, device=device)
+            self.jump_ops = [O.LatentRenoise(self.x.view(-1), self.coef, self.step_ctr, self.visit_ctr, self.seeds, jump=resample,
+                                             x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, xin_c=Cl, name="resample.jump")]
         self.health_prog: Optional[L.Program] = None
         self.prologue: Optional[L.Program] = None
         self.step: Optional[L.Program] = None
@@ -451,6 +469,8 @@ class SamplerPlan:
         self.prologue = O.build_program(self.prologue_ops)
         if self.health_ops:
             self.health_prog = O.build_program(self.health_ops)
+        if self.jump_ops:
+            self.jump = O.build_program(self.jump_ops)
         if self.fork_at is None:
             self.step = O.build_program(self.step_ops)
         else:
@@ -480,6 +500,16 @@ class SamplerPlan:
         main.wait_event(done)
         go(self.step_tail, main)
 
+    def launch_jump(self, stream: int, use_graph: bool = True) -> None:
+        """One forward jump of a resample plan on `stream` (raw hipStream_t), between two steps: its own captured graph, or eagerly."""
+        assert self.jump_ops, "this plan was built without resample"
+        if self.jump is None:
+            self.jump = O.build_program(self.jump_ops)
+        if use_graph:
+            self.jump.launch(stream)
+        else:
+            self.jump.run(stream)
+
     def health_table(self) -> Optional[torch.Tensor]:
         """The plan's health records on the device, fp32 {nonfinite, absmax, sum, sumsq} per view (view = scene * n_cam + cam):
         "trace": [num_steps, b * n_cam, 4], row s written by step s (rows of steps that have not run yet are zero);
@@ -501,11 +531,12 @@ class SamplerPlan:
         a running graph is not safe, so the device is drained first (evictions are rare: once per new batch geometry)."""
         if self.device is not None and torch.device(self.device).type == "cuda":
             torch.cuda.synchronize(self.device)
-        for prog in (self.prologue, self.step, self.step_cn, self.step_enc, self.step_tail):
+        for prog in (self.prologue, self.step, self.step_cn, self.step_enc, self.step_tail, self.jump):
             if prog is not None:
                 prog.destroy()
-        self.prologue = self.step = self.step_cn = self.step_enc = self.step_tail = None
+        self.prologue = self.step = self.step_cn = self.step_enc = self.step_tail = self.jump = None
         self.prologue_ops = self.step_ops = []
+        self.jump_ops = []
         self.health_ops, self.health_prog = [], None
         self.bld = None
         self.cond = self.temb_cn = self.temb_un = self.kv_cn = self.kv_un = None
@@ -513,11 +544,13 @@ class SamplerPlan:
     # ---- per-call inputs ----
     def load_inputs(self, latents: torch.Tensor, camera_param, text, bev_map, boxes, timesteps: torch.Tensor, coef: torch.Tensor,
                     given_mask: Optional[torch.Tensor] = None, given_latents: Optional[torch.Tensor] = None,
-                    keep_mask: Optional[torch.Tensor] = None):
+                    keep_mask: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None):
         """latents (b, n_cam, C, h, w) any float dtype; camera/text/map/boxes already hold the [uncond | cond] halves.
         given_mask (b, n_cam) bool + given_latents (b, n_cam, C, h, w): the known views of a given-view plan.
         keep_mask (b, n_cam, h, w) in [0, 1], a keep_regions plan only (validated by the caller; zero on views that are not given): the
-        first sample is m * add_noise(cond, noise, t_0) + (1 - m) * noise, with exact m == 1 / m == 0 taking the term itself."""
+        first sample is m * add_noise(cond, noise, t_0) + (1 - m) * noise, with exact m == 1 / m == 0 taking the term itself.
+        seeds (b,) int64, a resample plan only: one seed per scene, replicated over its views (the jump noise is shared across the views
+        of a scene like the initial noise); visit_ctr restarts at zero."""
         b, nc = self.b, self.n_cam
         assert latents.shape[:2] == (b, nc)
         xl = latents.to(self.device, F32).reshape(b * nc, *latents.shape[2:]).permute(0, 2, 3, 1).contiguous()
@@ -552,6 +585,12 @@ class SamplerPlan:
         self.temb_cn.t.copy_(t); self.temb_un.t.copy_(t)
         self.coef.copy_(coef.to(self.device, F32))
         self.step_ctr.zero_()
+        if self.resample is not None:
+            assert seeds is not None and tuple(seeds.shape) == (b,) and seeds.dtype == torch.int64, "seeds must be (b,) int64"
+            self.seeds.copy_(seeds.to(self.device).repeat_interleave(nc))
+            self.visit_ctr.zero_()
+        else:
+            assert seeds is None, "this plan was built without resample"
         if self._health is not None:
             self._health.zero_()
         if self.scheduler_kind == "unipc":

@@ -79,6 +79,9 @@ def op_bytes(op) -> float:
     if isinstance(op, O.LatentBlend):
         # 0 MFMA flops (op_flops), bytes only, every operand once: x read and written, cond, noise, the mask, the x_in copies
         return 2 * nb(op.x) + nb(op.cond) + nb(op.noise) + nb(op.mask) + nb(op.x_in)
+    if isinstance(op, O.LatentRenoise):
+        # 0 MFMA flops; x read and written, the seeds, the x_in copies (the noise is never in memory)
+        return 2 * nb(op.x) + nb(op.seeds) + nb(op.x_in)
     if isinstance(op, (O.Ew, O.Upsample, O.Layout)):
         return nb(op.X) + nb(op.Y) * (2 if getattr(op, "kind", 0) == 1 else 1)
     return 0.0

@@ -765,6 +765,61 @@ class LatentBlend:
         return self.opcode, d
 
 
+@dataclass
+class LatentRenoise:
+    """One forward jump of the sampler with device-side Gaussian noise (MdxRenoiseDesc, csrc/noise.hip), launched BETWEEN steps: with
+    c = step, v = visit (read on the device), r = coef[c - jump, col_t] / coef[c - 1, col_p] and sg = sqrt(max(0, 1 - r^2)),
+    x <- fma(r, x, sg * z), x_in refreshed as the scheduler ops do, then step <- c - jump and visit <- v + 1.  z is Philox4x32-10 +
+    Box-Muller of (seeds[g], v, e) for element e of group g (include/mdx.h has the mapping to the bit).  x fp32 [n]; seeds int64 / uint64
+    [groups], one per n / groups consecutive elements (a view); coef / step / x_in / cfg / xin_c: the scheduler op's; visit int32 [1].
+    col_t / col_p: 0, 2 of a DDIM table (the only one a jump is defined for: UniPC's multistep history does not survive it).
+    The build follows x_in's 16-bit type (dtype_code); with an fp32 x_in or none the two builds are the same kernel."""
+    x: torch.Tensor
+    coef: torch.Tensor                   # fp32 [steps, 4]
+    step: torch.Tensor                   # int32 [1], read and written
+    visit: torch.Tensor                  # int32 [1], read and written
+    seeds: torch.Tensor                  # int64 [groups]
+    jump: int
+    col_t: int = -1                      # -1: by the table's width (4 -> 0, 2)
+    col_p: int = -1
+    x_in: Optional[torch.Tensor] = None
+    cfg: bool = False
+    xin_c: int = 0
+    name: str = ""
+    opcode = L.OP_LATENT_RENOISE
+
+    COLUMNS = {4: (0, 2)}                # sqrt(abar) of a step's own timestep / of the next one in a DDIM coefficient row
+
+    def lower(self):
+        n = self.x.numel()
+        _chk(self.x.dtype == F32 and self.x.is_contiguous(), f"renoise {self.name}: x must be fp32, dense")
+        _chk(self.seeds.dtype in (torch.int64, torch.uint64) and self.seeds.is_contiguous() and self.seeds.numel() > 0 and n % self.seeds.numel() == 0,
+             f"renoise {self.name}: seeds must be int64, dense, with a size dividing n={n}")
+        _chk(self.coef.dtype == F32 and self.coef.dim() == 2 and self.coef.is_contiguous() and self.coef.shape[0] >= 1,
+             f"renoise {self.name}: coef fp32 [steps, ld]")
+        _chk(all(t.dtype == torch.int32 and t.numel() == 1 for t in (self.step, self.visit)), f"renoise {self.name}: step and visit int32 [1]")
+        _chk(isinstance(self.jump, int) and not isinstance(self.jump, bool) and self.jump >= 1, f"renoise {self.name}: jump={self.jump!r} must be an integer >= 1")
+        ld = self.coef.shape[1]
+        col_t, col_p = self.col_t, self.col_p
+        if col_t < 0 or col_p < 0:
+            _chk(ld in self.COLUMNS, f"renoise {self.name}: a coefficient table of width {ld} needs col_t / col_p")
+            col_t, col_p = self.COLUMNS[ld]
+        _chk(0 <= col_t < ld and 0 <= col_p < ld, f"renoise {self.name}: columns {col_t}, {col_p} of a table of width {ld}")
+        d = L.MdxRenoiseDesc()
+        d.x, d.x_in, d.coef, d.step_ptr, d.visit_ptr, d.seeds = _p(self.x), _p(self.x_in), _p(self.coef), _p(self.step), _p(self.visit), _p(self.seeds)
+        c = 2 if self.cfg else 1
+        if self.x_in is not None:
+            if self.x_in.dtype == F32:
+                _chk(self.x_in.is_contiguous() and self.x_in.numel() == c * n, f"renoise {self.name}: fp32 x_in must hold {c} x n elements")
+            else:
+                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.x_in.is_contiguous() and self.xin_c > 0, f"renoise {self.name}: 16-bit x_in must be [pixels, ld]")
+                _chk(self.x_in.shape[0] * self.xin_c == c * n and self.x_in.shape[1] >= self.xin_c, f"renoise {self.name}: 16-bit x_in shape")
+                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
+        d.n, d.group_elems, d.jump, d.n_rows, d.coef_ld, d.col_t, d.col_p = n, n // self.seeds.numel(), self.jump, self.coef.shape[0], ld, col_t, col_p
+        d.cfg = int(self.cfg)
+        return self.opcode, d
+
+
 def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, scale: Optional[float] = None, causal: bool = False,
          key_lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(scale * q k^T + mask) v per head on the GPU kernel behind mdx_sdpa_* (ops.Sdpa), on torch's current stream.

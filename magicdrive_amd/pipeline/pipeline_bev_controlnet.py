@@ -18,14 +18,14 @@ import inspect
 import json
 import os
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Union
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from .. import _lib
 from ..denoiser import PlanCache, SamplerPlan, device_stream
-from ..schedulers import DDIMScheduler, UniPCMultistepScheduler
+from ..schedulers import DDIMScheduler, UniPCMultistepScheduler, resample_actions
 
 
 @dataclass
@@ -131,6 +131,19 @@ class StableDiffusionBEVControlNetPipeline:
         # result is the model's own last-step output given that context, NOT the encoded input; a pixel-space composite with the
         # original pictures is left to the caller.  magicdrive_amd.dataset.regions.box_keep_mask builds the masks from projected boxes.
         self.keep_masks: Optional[List[List[Optional[torch.Tensor]]]] = None
+        # RePaint resampling of a kept-region edit (Lugmayr et al. 2022; with keep_masks only, DDIM only; an attribute like keep_masks).
+        # None (default): today's path, plan key included.  (jump_length, jump_n_sample), integers >= 1: the loop follows
+        # schedulers.resample_actions(num_steps, jump_length, jump_n_sample) — after the step at every jump_length-th index the sample is
+        # diffused forward again by jump_length steps with fresh Gaussian noise made on the device (ops.LatentRenoise, the plan's own
+        # captured graph; no host copy, no sync) and those steps are taken once more, jump_n_sample times in all: the model gets time to
+        # harmonise regenerated content with kept content.  A call costs actions.count("step") UNet evaluations instead of num_steps;
+        # callbacks and the progress bar count step launches.  One int64 seed per scene is drawn from the call's generator (from each
+        # scene's own in list form) AFTER the initial latents and shared by the scene's views; the noise of a jump depends on that seed,
+        # the number of jumps taken so far and the element's place in its view only, so a scene has the same jump noise alone and in a
+        # batch, on one stream or two.  health="trace" rows are indexed by step, so a revisited step overwrites its row; the final step
+        # is not blended on any visit.  UniPC is refused (NotImplementedError): a jump would invalidate its multistep history.
+        # Nobody has measured picture quality with trained weights on this path: the feature is the mechanism.
+        self.resample: Optional[Tuple[int, int]] = None
 
     # ---- construction / housekeeping the reference's callers use (misc/test_utils.py:94-138) ----
     @classmethod
@@ -330,16 +343,33 @@ class StableDiffusionBEVControlNetPipeline:
         return (cap, "scene", (cap, "scene")) if scene else (cap, True, (cap, "dynamic"))
 
     def _plan_key(self, n_scene, chunk, do_cfg, box_key, h, w, n_steps, guidance_scale, conditioning_scale, n_text, sched_kind, gv_mode, pdt, fork,
-                  health=None, regions=False):
+                  health=None, regions=False, resample=None):
         """Cache key of one scene chunk's SamplerPlan.  `health` enters as a trailing entry only when it is on: with the switch off the key is,
-        entry for entry, what it was before the switch existed.  Likewise `regions` (pipe.keep_masks set): a trailing ("regions",)."""
+        entry for entry, what it was before the switch existed.  Likewise `regions` (pipe.keep_masks set): a trailing ("regions",), and
+        `resample` (pipe.resample set; the jump length: jump_n_sample only shapes the loop): a trailing ("resample", jump_length)."""
         key = (n_scene, chunk, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(conditioning_scale), n_text, sched_kind,
                gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
         if health is not None:
             key = key + (("health", health),)
         if regions:
             key = key + (("regions",),)
+        if resample is not None:
+            key = key + (("resample", int(resample)),)
         return key
+
+    def _checked_resample(self) -> Tuple[int, int]:
+        """pipe.resample as (jump_length, jump_n_sample).  Every refusal is raised here, on the host, before any device work of the call."""
+        rs = self.resample
+        ok = isinstance(rs, (tuple, list)) and len(rs) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 1 for v in rs)
+        if not ok:
+            raise ValueError(f"resample={rs!r}: None or (jump_length, jump_n_sample), two integers >= 1")
+        if getattr(self, "keep_masks", None) is None:
+            raise ValueError("resample is set without keep_masks: resampling harmonises regenerated content with KEPT content "
+                             "(set pipe.keep_masks, or pipe.resample = None)")
+        if isinstance(self.scheduler, UniPCMultistepScheduler):
+            raise NotImplementedError("resample under UniPC: a jump moves the sample to another noise level, which invalidates UniPC's multistep history "
+                                      "(last sample, two model outputs); resampling is built for DDIMScheduler, whose step is stateless")
+        return int(rs[0]), int(rs[1])
 
     def _checked_keep_masks(self, given_view, height: int, width: int) -> torch.Tensor:
         """pipe.keep_masks as one (B, N_cam, h, w) fp32 tensor on the host: None on a view with a conditional latent -> ones, a view without
@@ -394,6 +424,9 @@ class StableDiffusionBEVControlNetPipeline:
         """`_given_view` = (conditional_latents, change_every_input) is how StableDiffusionBEVControlNetGivenViewPipeline reuses
         this body; not part of the reference signature."""
         keep = None
+        resample = None
+        if getattr(self, "resample", None) is not None:        # likewise, and before the masks are looked at
+            resample = self._checked_resample()
         if getattr(self, "keep_masks", None) is not None:      # refused or accepted on the host, before anything else of the call
             keep = self._checked_keep_masks(_given_view, height, width)
         if guess_mode:
@@ -447,6 +480,13 @@ class StableDiffusionBEVControlNetPipeline:
         timesteps = self.scheduler.timesteps
         num_channels_latents = self.unet.config.in_channels
         latents = self.prepare_latents(b, num_channels_latents, height, width, prompt_embeds.dtype, device, generator, latents)
+        jump_seeds = None
+        if resample is not None:      # one int64 seed per scene, drawn AFTER the initial latents from the same generator(s), on the host
+            if isinstance(generator, (list, tuple)):
+                jump_seeds = torch.cat([torch.empty(1, dtype=torch.int64, device=g.device).random_(generator=g).cpu() for g in generator])
+            else:
+                gdev = generator.device if isinstance(generator, torch.Generator) else torch.device("cpu")
+                jump_seeds = torch.empty(b, dtype=torch.int64, device=gdev).random_(generator=generator).cpu()
         self.prepare_extra_step_kwargs(generator, eta)
         assert camera_param.shape[0] == batch_size, f"Except {batch_size} camera params, but you have bs={len(camera_param)}"
         n_cam = camera_param.shape[1]
@@ -507,7 +547,7 @@ class StableDiffusionBEVControlNetPipeline:
             # built on the old PackedNet would keep running (and keep alive) the old ones
             # box_bucket: the key carries (capacity, "dynamic") in the place of L_box, scene_boxes (capacity, "scene"); neither / no boxes: today's key
             key = self._plan_key(s1 - s0, ci, do_cfg, box_key, h, w, n_steps, guidance_scale, controlnet_conditioning_scale, text.shape[1], sched_kind,
-                                 gv_mode, pdt, fork, health, regions=keep is not None)
+                                 gv_mode, pdt, fork, health, regions=keep is not None, resample=None if resample is None else resample[0])
             plan = self._plans.get(key)
             if plan is None:
                 with torch.cuda.device(device):
@@ -519,13 +559,15 @@ class StableDiffusionBEVControlNetPipeline:
                                        num_steps=n_steps, guidance_scale=guidance_scale,
                                        conditioning_scale=float(controlnet_conditioning_scale), n_text=text.shape[1], scheduler_kind=sched_kind,
                                        given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes, **({} if health is None else {"health": health}),
-                                       **({} if keep is None else {"keep_regions": True}))
+                                       **({} if keep is None else {"keep_regions": True}),
+                                       **({} if resample is None else {"resample": resample[0]}))
                     plan.compile()
                 self._plans.put(key, plan)
             plan.load_inputs(latents[s0:s1], rows(camera_param, s0, s1), rows(text, s0, s1), rows(image, s0, s1),
                              None if boxes is None else {k: rows(v, s0, s1) for k, v in boxes.items()}, timesteps,
                              self.scheduler.coefficient_table(), given_mask=None if gv_mask is None else gv_mask[s0:s1],
-                             given_latents=None if gv_lat is None else gv_lat[s0:s1], **({} if keep is None else {"keep_mask": keep[s0:s1]}))
+                             given_latents=None if gv_lat is None else gv_lat[s0:s1], **({} if keep is None else {"keep_mask": keep[s0:s1]}),
+                             **({} if jump_seeds is None else {"seeds": jump_seeds[s0:s1]}))
             plans.append(plan)
         with torch.cuda.device(device):                       # launches, graph replays and torch copies all target the pipeline's device
             main = torch.cuda.current_stream(device)
@@ -539,8 +581,21 @@ class StableDiffusionBEVControlNetPipeline:
             sts = [main.cuda_stream] + [s_.cuda_stream for s_ in side]
             for plan, st in zip(plans, sts):
                 plan.prologue.run(st)
-            with self.progress_bar(total=num_inference_steps) as bar:
-                for i, t in enumerate(timesteps):
+            # resample: the loop is an action list; a "step" entry is the launch below, unchanged, and a jump runs each chunk's own
+            # jump program on that chunk's stream.  Which step a launch takes is the device-side counter's business: i counts launches.
+            actions = ["step"] * n_steps if resample is None else resample_actions(n_steps, *resample)
+            n_launch = actions.count("step")
+            with self.progress_bar(total=num_inference_steps if resample is None else n_launch) as bar:
+                i, step_of = -1, 0      # launches so far - 1; the step the next launch takes (host mirror of step_ctr, for the callback's t)
+                for act in actions:
+                    if act != "step":
+                        for plan, st in zip(plans, sts):
+                            plan.launch_jump(st, self.use_graph)
+                        step_of -= act[1]
+                        continue
+                    i += 1
+                    t = timesteps[step_of]
+                    step_of += 1
                     if fork:                                  # two branches per step and chunk (ControlNet on the chunk's fork stream)
                         for plan, cst, fst in zip(plans, [main] + list(side), fside):
                             plan.launch_step(cst, fst, self.use_graph)

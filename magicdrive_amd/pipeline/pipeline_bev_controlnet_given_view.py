@@ -8,6 +8,8 @@ here both are branches of the fused CFG + DDIM kernel (MdxDdimDesc.gv_*), so the
 `pipe.keep_masks` (an attribute: the call signature is the reference's; default None = everything above, unchanged) keeps REGIONS of the
 known views: a B x N_cam list of None or (h, w) tensors in [0, 1] — the per-pixel, fractional form of the change_every_input=True
 branch, one ops.LatentBlend behind the scheduler op (StableDiffusionBEVControlNetPipeline.__init__ documents it).
+`pipe.resample = (jump_length, jump_n_sample)` (with keep_masks, DDIM only; default None) resamples such an edit the RePaint way: forward
+jumps with Gaussian noise made on the device (ops.LatentRenoise) between replays of the unchanged step graph (same places document it).
 """
 from __future__ import annotations
 

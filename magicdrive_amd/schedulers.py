@@ -19,6 +19,48 @@ import torch
 
 
 
+def resample_actions(num_steps: int, jump_length: int, jump_n_sample: int) -> list:
+    """The sampling loop of RePaint resampling (Lugmayr et al. 2022) as a list of "step" and ("jump", jump_length) entries.
+
+    Equivalent to the index list of RePaintScheduler.set_timesteps (third_party/diffusers/src/diffusers/schedulers/
+    scheduling_repaint.py): a reverse step at index t is the sampler's step s = num_steps - 1 - t; after the reverse step at an index
+    that is a multiple of jump_length (below num_steps - jump_length), the sample is diffused forward again by jump_length steps and
+    those steps are taken once more, jump_n_sample - 1 times at each such index.  Each ascending run of jump_length indices is ONE
+    jump entry (ops.LatentRenoise moves the sample and the step counter by the whole run).  jump_n_sample == 1 or jump_length >=
+    num_steps gives num_steps plain steps.  The step counter stays in [0, num_steps] along the list and ends at num_steps;
+    count("step") is the number of UNet evaluations of the call."""
+    for name, v in (("num_steps", num_steps), ("jump_length", jump_length), ("jump_n_sample", jump_n_sample)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name}={v!r} must be an integer >= 1")
+    num_steps, jump_length, jump_n_sample = int(num_steps), int(jump_length), int(jump_n_sample)
+    left = {t: jump_n_sample - 1 for t in range(0, num_steps - jump_length, jump_length)}     # jumps still to take behind index t
+    actions: list = []
+    t = num_steps
+    while t >= 1:
+        t -= 1
+        actions.append("step")
+        if left.get(t, 0) > 0:
+            left[t] -= 1
+            actions.append(("jump", jump_length))
+            t += jump_length
+    return actions
+
+
+def resample_indices(num_steps: int, actions) -> list:
+    """An action list of resample_actions expanded back to RePaint's index list (one entry per reverse step, jump_length ascending
+    entries per jump): what RePaintScheduler.set_timesteps returns for the same arguments."""
+    out, c = [], 0                      # c: the step counter = reverse steps taken minus steps jumped back
+    for a in actions:
+        if a == "step":
+            out.append(num_steps - 1 - c)
+            c += 1
+        else:
+            _, j = a
+            out.extend(range(num_steps - c + 1, num_steps - c + j + 1))      # the last reverse step was at index num_steps - c
+            c -= j
+    return out
+
+
 class SchedulerOutput:
     """`scheduler.step(...)` result (diffusers' SchedulerOutput: `.prev_sample`)."""
 

@@ -5,7 +5,7 @@ load a checkpoint in the reference layout, read the training run's hydra overrid
 
   python tools/sample.py --ckpt <ckpt dir with unet/ controlnet/ hydra/overrides.yaml> --sd15 <stable-diffusion-v1-5 dir> \
          --data <folder of *.pth> --out <dir> [key=value overrides as for tools/test.py] [--scheduler unipc|ddim] [--prompt-embeds]
-         [--cond-on-view] [--regenerate-boxes [--region-dilate N]]
+         [--cond-on-view] [--regenerate-boxes [--region-dilate N] [--resample JL,JN]]
 
 --cond-on-view is demo/run_cond_on_view.py:34-120: the pipe class becomes StableDiffusionBEVControlNetGivenViewPipeline, the ground-truth
 views of every sample (`img` of the `.pth`) are encoded with the pipeline's VAE (`vae.encode(x).latent_dist.mean * scaling_factor`, on
@@ -17,6 +17,9 @@ boxes (magicdrive_amd.dataset.box_keep_mask: 1 - coverage of each latent pixel b
 pixels, default 1) — lets the sampler regenerate the boxes and keep everything else.  `validation_times` generations, one pipe() call each,
 seeded as the plain loop is (there is no "view ti given" rule), the same files and index.json.  The kept background is the model's own
 last-step output given the known latents, not the encoded input; compositing with the original pictures is left to the caller.
+--resample JL,JN (with --regenerate-boxes and --scheduler ddim only) sets pipe.resample = (jump_length, jump_n_sample): RePaint resampling,
+which gives the model time to harmonise the regenerated boxes with what is kept at the price of more UNet evaluations per call
+(INTEGRATION.md §1); index.json then carries "resample": [JL, JN].  Without the flag the output is byte for byte what it was.
 
 No hydra / omegaconf / mmdet3d: the config tree of the reference is not rebuilt (SURVEY.md §8 out of scope) — only the handful of
 keys the sampling loop reads are resolved, in the reference's order (checkpoint overrides first, command line last, tools/test.py:46-54):
@@ -301,6 +304,8 @@ def main(argv=None):
     ap.add_argument("--regenerate-boxes", action="store_true", help="box editing: all ground-truth views are encoded and given, pipe.keep_masks keeps every latent "
                     "pixel outside the sample's projected boxes (INTEGRATION.md §1); validation_times generations, seeded as the plain loop")
     ap.add_argument("--region-dilate", type=int, default=1, help="--regenerate-boxes: grow the regenerated region by N latent pixels (default 1)")
+    ap.add_argument("--resample", default=None, metavar="JL,JN", help="--regenerate-boxes with --scheduler ddim: RePaint resampling, pipe.resample = (jump_length, "
+                    "jump_n_sample), two integers >= 1 (INTEGRATION.md §1); recorded in index.json")
     ap.add_argument("--box-bucket", type=int, default=None, help="one sampler plan per bucket of N padded box counts (pipe.box_bucket, INTEGRATION.md §1): the "
                     "padded box count changes with almost every batch of a validation run; default: an exact plan per count")
     ap.add_argument("--scene-boxes", action="store_true", help="every scene of a batch attends to its own boxes only (pipe.scene_boxes, INTEGRATION.md §1): "
@@ -321,6 +326,16 @@ def main(argv=None):
         raise SystemExit("--regenerate-boxes gives every view with a mask; --cond-on-view gives view ti whole: pass one of the two")
     if a.region_dilate < 0:
         raise SystemExit("--region-dilate must be >= 0")
+    resample = None
+    if a.resample is not None:
+        if not a.regenerate_boxes:
+            raise SystemExit("--resample harmonises a kept-region edit: it is valid with --regenerate-boxes only")
+        if a.scheduler != "ddim":
+            raise SystemExit("--resample needs --scheduler ddim: a jump would invalidate UniPC's multistep history")
+        parts = a.resample.split(",")
+        if len(parts) != 2 or not all(p_.strip().isdigit() and int(p_) >= 1 for p_ in parts):
+            raise SystemExit(f"--resample {a.resample!r}: JL,JN, two integers >= 1")
+        resample = (int(parts[0]), int(parts[1]))
     given_view = a.cond_on_view or a.regenerate_boxes
     if a.pipe_factory:
         import importlib
@@ -334,6 +349,8 @@ def main(argv=None):
         pipe.box_bucket = a.box_bucket
     if a.scene_boxes:
         pipe.scene_boxes = True
+    if resample is not None:
+        pipe.resample = resample
     health_on = a.health != "off"
     if health_on:
         pipe.health, pipe.health_action = "trace", "flag"
@@ -392,7 +409,8 @@ def main(argv=None):
     if rank == 0:
         index.sort(key=lambda r_: (r_["scene"], r_["gen"]))
         with open(os.path.join(a.out, "index.json"), "w") as f:
-            json.dump(dict(world=world, seed=run["seed"], gather_images=bool(a.gather_images), generations=index), f, indent=1)
+            json.dump(dict(world=world, seed=run["seed"], gather_images=bool(a.gather_images), **({} if resample is None else {"resample": list(resample)}),
+                           generations=index), f, indent=1)
         print(f"sampled {len(data)} scenes x {run['validation_times'] - (1 if a.cond_on_view else 0)} on {world} rank(s) -> {a.out}")
     n_bad = n_bad_local
     if health_on and rank == 0:
