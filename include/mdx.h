@@ -402,8 +402,9 @@ int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream);
  *   xin_ld  > 0 : x_in is bf16 channels-last with pixel stride xin_ld >= xin_c (x has xin_c channels per
  *                 pixel; the pad channels are never written) — the layout conv_in's MFMA path reads.
  * Requirements (MDX_EINVAL; the same hold for mdx_cfg_unipc_step): x, eps, coef, step_ptr 4-byte aligned; xin_c, xin_ld, gv_last_step fit a
- * 32-bit int; xin_ld > 0 needs 0 < xin_c <= xin_ld and xin_c dividing n; a given-view mode needs gv_noise (mode 1: also gv_cond) and
- * gv_view_elems dividing n.
+ * 32-bit int; xin_ld is not negative; x_in at its element's alignment (4 / 2 bytes); xin_ld > 0 needs 0 < xin_c <= xin_ld and xin_c
+ * dividing n; a given-view mode needs gv_noise (mode 1: also gv_cond) and gv_view_elems dividing n.  The x_in clauses are one check for
+ * every op that refreshes x_in (these two, mdx_latent_blend_*, mdx_latent_renoise_*): same rule, same message behind the op's name.
  */
 typedef struct MdxDdimDesc {
     float* x; const float* eps; const float* coef; int32_t* step_ptr; void* x_in; void* reserved_p;

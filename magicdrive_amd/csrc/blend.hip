@@ -10,39 +10,24 @@
 //
 // Two instances of one body: VEC takes four consecutive elements per thread with 16-byte accesses of x / cond / noise (the launcher asks
 // for 16-byte-aligned pointers and mask_elems % 4 == 0, so the four share one mask entry and n % 4 == 0); the other takes one element per
-// thread.  Per element the arithmetic is the same function: same bits.  x_in is refreshed element by element as the scheduler kernels
-// do (its pixel stride need not keep four channels together).  No atomics, 64-bit addressing, one launch; the work is ~7 fp32 streams
-// of n elements: at the plan's n = views * h * w * 4 a few microseconds behind a step of milliseconds.
+// thread.  Per element the arithmetic is the same function: same bits.  x_in is refreshed element by element through store_xin
+// (latent.h: the one copy of the refresh, shared with the scheduler kernels; its pixel stride need not keep four channels together).
+// No atomics, 64-bit addressing, one launch; the work is ~7 fp32 streams of n elements: at the plan's n = views * h * w * 4 a few
+// microseconds behind a step of milliseconds.
 #include "common.h"
 #include "launch.h"
+#include "latent.h"
 
 namespace mdx {
 
 #define BL_T 256
 
-struct BlendParams { float* x; const float* cond; const float* noise; const float* mask; const float* coef; const int* step; void* x_in;
-                     long n, mask_elems; int coef_ld, col_a, col_s, last, cfg, xin_c, xin_ld; };
+struct BlendParams { float* x; const float* cond; const float* noise; const float* mask; const float* coef; const int* step;
+                     long mask_elems; int coef_ld, col_a, col_s, last; XinDst xin; };
 
 __device__ __forceinline__ float blend_value(float m, float a, float sg, float c, float nz, float x) {
     const float t = renoise_f(a, c, sg, nz);
     return m == 1.0f ? t : __builtin_fmaf(m, t - x, x);
-}
-
-// the model-input copies of element i, exactly as ddim_kernel / unipc_kernel write them
-__device__ __forceinline__ void blend_xin(const BlendParams& p, long i, float v) {
-    if (!p.x_in) return;
-    if (p.xin_ld > 0) {
-        const long px = i / p.xin_c;
-        const int ch = (int)(i - px * p.xin_c);
-        bf16_t* xi = (bf16_t*)p.x_in;
-        const bf16_t h = f2bf(v);
-        xi[px * p.xin_ld + ch] = h;
-        if (p.cfg) xi[(p.n / p.xin_c + px) * p.xin_ld + ch] = h;
-    } else {
-        float* xi = (float*)p.x_in;
-        xi[i] = v;
-        if (p.cfg) xi[p.n + i] = v;
-    }
 }
 
 template <bool VEC>
@@ -51,7 +36,7 @@ __global__ __launch_bounds__(BL_T) void blend_kernel(BlendParams p) {
     if (s < 0 || s >= p.last) return;                           // uniform over the launch: nothing is written
     const long q = (long)blockIdx.x * BL_T + threadIdx.x;
     const long i = VEC ? 4 * q : q;
-    if (i >= p.n) return;                                       // VEC: n % 4 == 0, so i < n means i + 3 < n
+    if (i >= p.xin.n) return;                                   // VEC: n % 4 == 0, so i < n means i + 3 < n
     const float m = p.mask[i / p.mask_elems];                   // VEC: mask_elems % 4 == 0, one entry for the four
     if (m == 0.0f) return;
     const float a = p.coef[(long)s * p.coef_ld + p.col_a], sg = p.coef[(long)s * p.coef_ld + p.col_s];
@@ -65,11 +50,11 @@ __global__ __launch_bounds__(BL_T) void blend_kernel(BlendParams p) {
         y.z = blend_value(m, a, sg, c.z, nz.z, x.z);
         y.w = blend_value(m, a, sg, c.w, nz.w, x.w);
         *reinterpret_cast<float4*>(p.x + i) = y;
-        blend_xin(p, i, y.x); blend_xin(p, i + 1, y.y); blend_xin(p, i + 2, y.z); blend_xin(p, i + 3, y.w);
+        store_xin(p.xin, i, y.x); store_xin(p.xin, i + 1, y.y); store_xin(p.xin, i + 2, y.z); store_xin(p.xin, i + 3, y.w);
     } else {
         const float y = blend_value(m, a, sg, p.cond[i], p.noise[i], p.x[i]);
         p.x[i] = y;
-        blend_xin(p, i, y);
+        store_xin(p.xin, i, y);
     }
 }
 
@@ -92,22 +77,18 @@ extern "C" int mdx_latent_blend_bf16(const MdxBlendDesc* d, void* stream) {
     if (!d->step_ptr) return set_error(MDX_EINVAL, "%s: step_ptr must not be NULL", op);
     MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "cond", d->cond, 4)); MDX_NEED(need_aligned(op, "noise", d->noise, 4));
     MDX_NEED(need_aligned(op, "mask", d->mask, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4)); MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4));
-    MDX_NEED(need_int(op, "xin_c", d->xin_c)); MDX_NEED(need_int(op, "xin_ld", d->xin_ld)); MDX_NEED(need_int(op, "coef_ld", d->coef_ld));
-    MDX_NEED(need_int(op, "last_step", d->last_step));
-    if (d->xin_ld < 0) return set_error(MDX_EINVAL, "%s: xin_ld=%ld must not be negative", op, (long)d->xin_ld);
-    MDX_NEED(need_aligned(op, "x_in", d->x_in, d->xin_ld > 0 ? 2 : 4));
+    MDX_NEED(need_int(op, "coef_ld", d->coef_ld)); MDX_NEED(need_int(op, "last_step", d->last_step));
     if (d->n < 0) return set_error(MDX_EINVAL, "%s: n=%ld must not be negative", op, (long)d->n);
     if (d->mask_elems < 1 || d->n % d->mask_elems) return set_error(MDX_EINVAL, "%s: mask_elems=%ld must be >= 1 and divide n=%ld", op, (long)d->mask_elems, (long)d->n);
     if (d->col_a < 0 || d->col_a >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_a=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_a, (long)d->coef_ld);
     if (d->col_s < 0 || d->col_s >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_s=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_s, (long)d->coef_ld);
     if (d->cfg != 0 && d->cfg != 1) return set_error(MDX_EINVAL, "%s: cfg=%ld must be 0 or 1", op, (long)d->cfg);
-    if (d->xin_ld > 0 && (d->xin_c <= 0 || d->xin_c > d->xin_ld || d->n % d->xin_c))
-        return set_error(MDX_EINVAL, "%s: xin_c=%ld must be in (0, xin_ld=%ld] and divide n=%ld", op, (long)d->xin_c, (long)d->xin_ld, (long)d->n);
+    MDX_NEED(need_xin(op, d));
     if (d->n == 0) return MDX_OK;
-    BlendParams p{d->x, d->cond, d->noise, d->mask, d->coef, d->step_ptr, d->x_in, d->n, d->mask_elems, (int)d->coef_ld, (int)d->col_a, (int)d->col_s,
-                  (int)d->last_step, (int)d->cfg, (int)d->xin_c, (int)d->xin_ld};
+    BlendParams p{d->x, d->cond, d->noise, d->mask, d->coef, d->step_ptr, d->mask_elems, (int)d->coef_ld, (int)d->col_a, (int)d->col_s,
+                  (int)d->last_step, xin_of(d)};
     const bool vec = (((uintptr_t)d->x | (uintptr_t)d->cond | (uintptr_t)d->noise) & 15) == 0 && d->mask_elems % 4 == 0;
-    const long work = vec ? p.n / 4 : p.n;
+    const long work = vec ? d->n / 4 : d->n;
     const long blocks = (work + BL_T - 1) / BL_T;
     if (blocks > 0x7fffffffL) return set_error(MDX_EINVAL, "%s: n=%ld needs more than 2^31 - 1 workgroups", op, (long)d->n);
     hipStream_t st = (hipStream_t)stream;

@@ -5,6 +5,7 @@
 // 16-byte vectorised where the layout allows, fp32 math.  Reference call sites: include/mdx.h.
 #include "common.h"
 #include "launch.h"
+#include "latent.h"
 #include "options.h"
 
 namespace mdx {
@@ -410,89 +411,47 @@ __global__ __launch_bounds__(256) void timeemb_kernel(TimeEmbParams p) {
     if (p.y_f32) ((float*)p.Y)[i * p.ldy + j] = out; else ((bf16_t*)p.Y)[i * p.ldy + j] = f2bf(out);
 }
 
-struct DdimParams { float* x; const float* eps; const float* coef; int* step; void* x_in; long n; int cfg; float g; int xin_c, xin_ld;
-                    const float* gv_cond; const float* gv_noise; const unsigned char* gv_mask; int gv_mode; long gv_view; int gv_last; };
+struct DdimParams { float* x; const float* eps; const float* coef; int* step; float g; XinDst xin; GivenViews gv; };
 
 __global__ __launch_bounds__(256) void ddim_kernel(DdimParams p) {
     long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = p.xin.n;
     const int step = *p.step;
-    if (i < p.n && step < 0) {          // a row index of -1 = "timestep not in the scheduler's list" (DDIMScheduler.step with a device timestep):
+    if (i < n && step < 0) {            // a row index of -1 = "timestep not in the scheduler's list" (DDIMScheduler.step with a device timestep):
         p.x[i] = __builtin_nanf("");     // poison the result instead of silently using row 0
         return;
     }
-    if (i < p.n) {
+    if (i < n) {
         const float* c = p.coef + 4 * step;
-        float e;
-        if (p.cfg) {
-            float eu = p.eps[i], ec = p.eps[p.n + i];
-            e = eu + p.g * (ec - eu);
-        } else {
-            e = p.eps[i];
-        }
-        // given views (pipeline_bev_controlnet_given_view.py:263-291, 380-390; include/mdx.h: MdxDdimDesc.gv_*)
-        const bool given = p.gv_mode != 0 && p.gv_mask[i / p.gv_view] != 0;
-        if (given && p.gv_mode == 2) e = p.gv_noise[i];
+        float e = cfg_eps(p.eps, n, p.xin.cfg, p.g, i);
+        const bool given = gv_given(p.gv, i);
+        if (given && p.gv.mode == 2) e = p.gv.noise[i];
         float x = p.x[i];
         float x0 = (x - c[1] * e) / c[0];
-        float xn = c[2] * x0 + c[3] * e;
-        if (given && p.gv_mode == 1 && step < p.gv_last) xn = renoise_f(c[2], p.gv_cond[i], c[3], p.gv_noise[i]);
+        float xn = gv_renoise(p.gv, given, step, i, c[2], c[3], c[2] * x0 + c[3] * e);
         p.x[i] = xn;
-        if (p.x_in) {
-            if (p.xin_ld > 0) {          // bf16 channels-last copy with padded pixel stride
-                long px = i / p.xin_c;
-                int c = (int)(i - px * p.xin_c);
-                bf16_t* xi = (bf16_t*)p.x_in;
-                bf16_t v = f2bf(xn);
-                xi[px * p.xin_ld + c] = v;
-                if (p.cfg) xi[(p.n / p.xin_c + px) * p.xin_ld + c] = v;
-            } else {
-                float* xi = (float*)p.x_in;
-                xi[i] = xn;
-                if (p.cfg) xi[p.n + i] = xn;
-            }
-        }
+        store_xin(p.xin, i, xn);
     }
 }
-struct UniPCParams { float* x; const float* eps; const float* coef; int* step; void* x_in; float* x_last; float* m1; float* m2; long n; int cfg; float g; int xin_c, xin_ld;
-                     const float* gv_cond; const float* gv_noise; const unsigned char* gv_mask; int gv_mode; long gv_view; int gv_last; };
+struct UniPCParams { float* x; const float* eps; const float* coef; int* step; float* x_last; float* m1; float* m2; float g; XinDst xin; GivenViews gv; };
 
 __global__ __launch_bounds__(256) void unipc_kernel(UniPCParams p) {
     long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = p.xin.n;
     const int step = *p.step;
-    if (i >= p.n) return;
+    if (i >= n) return;
     const float* c = p.coef + 12 * step;
-    float e;
-    if (p.cfg) {
-        float eu = p.eps[i], ec = p.eps[p.n + i];
-        e = eu + p.g * (ec - eu);
-    } else {
-        e = p.eps[i];
-    }
-    // given views (pipeline_bev_controlnet_given_view.py:263-291, 380-390 under the scheduler build_pipe installs; MdxUniPCDesc.gv_*)
-    const bool given = p.gv_mode != 0 && p.gv_mask[i / p.gv_view] != 0;
-    if (given && p.gv_mode == 2) e = p.gv_noise[i];
+    float e = cfg_eps(p.eps, n, p.xin.cfg, p.g, i);
+    const bool given = gv_given(p.gv, i);
+    if (given && p.gv.mode == 2) e = p.gv.noise[i];
     const float x = p.x[i];
     const float m1 = p.m1[i], m2 = p.m2[i];
     const float mt = c[0] * x + c[1] * e;
     float xc = x;
     if (c[2] != 0.f) xc = c[3] * p.x_last[i] + c[4] * m1 + c[5] * m2 + c[6] * mt;
-    float xn = c[7] * xc + c[8] * mt + c[9] * m1;
-    if (given && p.gv_mode == 1 && step < p.gv_last) xn = renoise_f(c[10], p.gv_cond[i], c[11], p.gv_noise[i]);
+    const float xn = gv_renoise(p.gv, given, step, i, c[10], c[11], c[7] * xc + c[8] * mt + c[9] * m1);
     p.x[i] = xn; p.x_last[i] = xc; p.m2[i] = m1; p.m1[i] = mt;
-    if (p.x_in) {
-        if (p.xin_ld > 0) {
-            long px = i / p.xin_c;
-            int ch = (int)(i - px * p.xin_c);
-            bf16_t* xi = (bf16_t*)p.x_in;
-            bf16_t v = f2bf(xn);
-            xi[px * p.xin_ld + ch] = v;
-            if (p.cfg) xi[(p.n / p.xin_c + px) * p.xin_ld + ch] = v;
-        } else {
-            float* xi = (float*)p.x_in;
-            xi[i] = xn;
-            if (p.cfg) xi[p.n + i] = xn;
-        }
-    }
+    store_xin(p.xin, i, xn);
 }
 
 // Separate 1-thread launch so every block of ddim_kernel has read *step before it changes.
@@ -638,18 +597,17 @@ extern "C" int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream) {
 }
 
 extern "C" int mdx_cfg_ddim_step(const MdxDdimDesc* d, void* stream) {
-    if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr) return set_error(MDX_EINVAL, "mdx_cfg_ddim_step: null operand");
-    MDX_NEED(need_int("mdx_cfg_ddim_step", "xin_c", d->xin_c)); MDX_NEED(need_int("mdx_cfg_ddim_step", "xin_ld", d->xin_ld)); MDX_NEED(need_int("mdx_cfg_ddim_step", "gv_last_step", d->gv_last_step));
-    MDX_NEED(need_aligned("mdx_cfg_ddim_step", "x", d->x, 4)); MDX_NEED(need_aligned("mdx_cfg_ddim_step", "eps", d->eps, 4)); MDX_NEED(need_aligned("mdx_cfg_ddim_step", "coef", d->coef, 4));
-    MDX_NEED(need_aligned("mdx_cfg_ddim_step", "step_ptr", d->step_ptr, 4));
-    DdimParams p{d->x, d->eps, d->coef, d->step_ptr, d->x_in, d->n, (int)d->cfg, (float)d->guidance, (int)d->xin_c, (int)d->xin_ld,
-                 d->gv_cond, d->gv_noise, d->gv_mask, d->gv_mask ? (int)d->gv_mode : 0, d->gv_view_elems, (int)d->gv_last_step};
-    if (p.xin_ld > 0 && (p.xin_c <= 0 || p.xin_ld < p.xin_c || p.n % p.xin_c)) return set_error(MDX_EINVAL, "ddim: bad x_in channel layout");
-    if (p.gv_mode != 0 && (p.gv_mode < 0 || p.gv_mode > 2 || !p.gv_noise || (p.gv_mode == 1 && !p.gv_cond) || p.gv_view <= 0 || p.n % p.gv_view))
-        return set_error(MDX_EINVAL, "ddim: given-view mode %d needs gv_noise (+ gv_cond for mode 1) and gv_view_elems dividing n", p.gv_mode);
-    if (p.n <= 0) return MDX_OK;
+    const char* op = "mdx_cfg_ddim_step";
+    if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr) return set_error(MDX_EINVAL, "%s: null operand", op);
+    MDX_NEED(need_int(op, "gv_last_step", d->gv_last_step));
+    MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "eps", d->eps, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4));
+    MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4));
+    MDX_NEED(need_xin(op, d));
+    MDX_NEED(need_given_views("ddim", d));
+    DdimParams p{d->x, d->eps, d->coef, d->step_ptr, (float)d->guidance, xin_of(d), given_views_of(d)};
+    if (d->n <= 0) return MDX_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ddim_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(ddim_kernel, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, st, p);
     int rc = check_launch("ddim_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, p.step);
@@ -657,19 +615,17 @@ extern "C" int mdx_cfg_ddim_step(const MdxDdimDesc* d, void* stream) {
 }
 
 extern "C" int mdx_cfg_unipc_step(const MdxUniPCDesc* d, void* stream) {
-    if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr || !d->x_last || !d->m1 || !d->m2)
-        return set_error(MDX_EINVAL, "mdx_cfg_unipc_step: null operand");
-    MDX_NEED(need_int("mdx_cfg_unipc_step", "xin_c", d->xin_c)); MDX_NEED(need_int("mdx_cfg_unipc_step", "xin_ld", d->xin_ld)); MDX_NEED(need_int("mdx_cfg_unipc_step", "gv_last_step", d->gv_last_step));
-    MDX_NEED(need_aligned("mdx_cfg_unipc_step", "x", d->x, 4)); MDX_NEED(need_aligned("mdx_cfg_unipc_step", "eps", d->eps, 4)); MDX_NEED(need_aligned("mdx_cfg_unipc_step", "coef", d->coef, 4));
-    MDX_NEED(need_aligned("mdx_cfg_unipc_step", "step_ptr", d->step_ptr, 4));
-    UniPCParams p{d->x, d->eps, d->coef, d->step_ptr, d->x_in, d->x_last, d->m1, d->m2, d->n, (int)d->cfg, (float)d->guidance, (int)d->xin_c, (int)d->xin_ld,
-                  d->gv_cond, d->gv_noise, d->gv_mask, d->gv_mask ? (int)d->gv_mode : 0, d->gv_view_elems, (int)d->gv_last_step};
-    if (p.xin_ld > 0 && (p.xin_c <= 0 || p.xin_ld < p.xin_c || p.n % p.xin_c)) return set_error(MDX_EINVAL, "unipc: bad x_in channel layout");
-    if (p.gv_mode != 0 && (p.gv_mode < 0 || p.gv_mode > 2 || !p.gv_noise || (p.gv_mode == 1 && !p.gv_cond) || p.gv_view <= 0 || p.n % p.gv_view))
-        return set_error(MDX_EINVAL, "unipc: given-view mode %d needs gv_noise (+ gv_cond for mode 1) and gv_view_elems dividing n", p.gv_mode);
-    if (p.n <= 0) return MDX_OK;
+    const char* op = "mdx_cfg_unipc_step";
+    if (!d || !d->x || !d->eps || !d->coef || !d->step_ptr || !d->x_last || !d->m1 || !d->m2) return set_error(MDX_EINVAL, "%s: null operand", op);
+    MDX_NEED(need_int(op, "gv_last_step", d->gv_last_step));
+    MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "eps", d->eps, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4));
+    MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4));
+    MDX_NEED(need_xin(op, d));
+    MDX_NEED(need_given_views("unipc", d));
+    UniPCParams p{d->x, d->eps, d->coef, d->step_ptr, d->x_last, d->m1, d->m2, (float)d->guidance, xin_of(d), given_views_of(d)};
+    if (d->n <= 0) return MDX_OK;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(unipc_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, st, p);
+    hipLaunchKernelGGL(unipc_kernel, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, st, p);
     int rc = check_launch("unipc_kernel");
     if (rc) return rc;
     hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, st, p.step);

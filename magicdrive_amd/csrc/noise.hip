@@ -17,17 +17,19 @@
 // Two instances of one body, one thread per block of four e: VEC moves the four with one 16-byte access (the launcher asks for a
 // 16-byte-aligned x and group_elems % 4 == 0, so every block is whole and aligned); the other moves 1 .. 4 elements one by one (the last
 // block of a group whose size is no multiple of four is partial).  Per element the arithmetic is the same function: same bits.  x_in is
-// refreshed element by element as the scheduler kernels do.  No atomics, 64-bit addressing.  The transcendentals are the accurate ones
-// (logf, sqrtf, sincospif on the EXACT argument 2 u2): |z - fp64| stays below 1e-5 up to the largest radius sqrt(48 ln 2).
+// refreshed element by element through store_xin (latent.h: the one copy of the refresh, shared with the scheduler kernels).  No atomics,
+// 64-bit addressing.  The transcendentals are the accurate ones (logf, sqrtf, sincospif on the EXACT argument 2 u2): |z - fp64| stays
+// below 1e-5 up to the largest radius sqrt(48 ln 2).
 #include "common.h"
 #include "launch.h"
+#include "latent.h"
 
 namespace mdx {
 
 #define RN_T 256
 
-struct RenoiseParams { float* x; void* x_in; const float* coef; int* step; int* visit; const unsigned long long* seeds;
-                       long n, group, bpg; int jump, n_rows, coef_ld, col_t, col_p, cfg, xin_c, xin_ld; };
+struct RenoiseParams { float* x; const float* coef; int* step; int* visit; const unsigned long long* seeds;
+                       long group, bpg; int jump, n_rows, coef_ld, col_t, col_p; XinDst xin; };
 
 __device__ __forceinline__ bool renoise_in_range(int c, int jump, int n_rows) { return jump >= 1 && c >= 1 && c <= n_rows && c - jump >= 0; }
 
@@ -57,29 +59,12 @@ __device__ __forceinline__ float renoise_value(float r, float sg, float x, float
     return __builtin_fmaf(r, x, nz);
 }
 
-// the model-input copies of element i, exactly as ddim_kernel / unipc_kernel / blend_kernel write them
-__device__ __forceinline__ void renoise_xin(const RenoiseParams& p, long i, float v) {
-    if (!p.x_in) return;
-    if (p.xin_ld > 0) {
-        const long px = i / p.xin_c;
-        const int ch = (int)(i - px * p.xin_c);
-        bf16_t* xi = (bf16_t*)p.x_in;
-        const bf16_t h = f2bf(v);
-        xi[px * p.xin_ld + ch] = h;
-        if (p.cfg) xi[(p.n / p.xin_c + px) * p.xin_ld + ch] = h;
-    } else {
-        float* xi = (float*)p.x_in;
-        xi[i] = v;
-        if (p.cfg) xi[p.n + i] = v;
-    }
-}
-
 template <bool VEC>
 __global__ __launch_bounds__(RN_T) void renoise_kernel(RenoiseParams p) {
     const int c = *p.step, v = *p.visit;
     const long q = (long)blockIdx.x * RN_T + threadIdx.x;       // block of four relative indices: group g, block k of the group
     const long g = q / p.bpg;
-    if (g >= p.n / p.group) return;
+    if (g >= p.xin.n / p.group) return;
     const long k = q - g * p.bpg;
     const long e0 = 4 * k;
     const long i0 = g * p.group + e0;
@@ -105,14 +90,14 @@ __global__ __launch_bounds__(RN_T) void renoise_kernel(RenoiseParams p) {
         y.z = renoise_value(r, sg, x.z, z[2]);
         y.w = renoise_value(r, sg, x.w, z[3]);
         *reinterpret_cast<float4*>(p.x + i0) = y;
-        renoise_xin(p, i0, y.x); renoise_xin(p, i0 + 1, y.y); renoise_xin(p, i0 + 2, y.z); renoise_xin(p, i0 + 3, y.w);
+        store_xin(p.xin, i0, y.x); store_xin(p.xin, i0 + 1, y.y); store_xin(p.xin, i0 + 2, y.z); store_xin(p.xin, i0 + 3, y.w);
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j < cnt) {
                 const float y = renoise_value(r, sg, p.x[i0 + j], z[j]);
                 p.x[i0 + j] = y;
-                renoise_xin(p, i0 + j, y);
+                store_xin(p.xin, i0 + j, y);
             }
         }
     }
@@ -144,10 +129,7 @@ extern "C" int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream) {
     if (!d->seeds) return set_error(MDX_EINVAL, "%s: seeds must not be NULL", op);
     MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4)); MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4));
     MDX_NEED(need_aligned(op, "visit_ptr", d->visit_ptr, 4)); MDX_NEED(need_aligned(op, "seeds", d->seeds, 8));
-    MDX_NEED(need_int(op, "xin_c", d->xin_c)); MDX_NEED(need_int(op, "xin_ld", d->xin_ld)); MDX_NEED(need_int(op, "coef_ld", d->coef_ld));
-    MDX_NEED(need_int(op, "jump", d->jump)); MDX_NEED(need_int(op, "n_rows", d->n_rows));
-    if (d->xin_ld < 0) return set_error(MDX_EINVAL, "%s: xin_ld=%ld must not be negative", op, (long)d->xin_ld);
-    MDX_NEED(need_aligned(op, "x_in", d->x_in, d->xin_ld > 0 ? 2 : 4));
+    MDX_NEED(need_int(op, "coef_ld", d->coef_ld)); MDX_NEED(need_int(op, "jump", d->jump)); MDX_NEED(need_int(op, "n_rows", d->n_rows));
     if (d->n < 0) return set_error(MDX_EINVAL, "%s: n=%ld must not be negative", op, (long)d->n);
     if (d->group_elems < 1 || d->n % d->group_elems) return set_error(MDX_EINVAL, "%s: group_elems=%ld must be >= 1 and divide n=%ld", op, (long)d->group_elems, (long)d->n);
     if (d->jump < 1) return set_error(MDX_EINVAL, "%s: jump=%ld must be >= 1", op, (long)d->jump);
@@ -155,14 +137,13 @@ extern "C" int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream) {
     if (d->col_t < 0 || d->col_t >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_t=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_t, (long)d->coef_ld);
     if (d->col_p < 0 || d->col_p >= d->coef_ld) return set_error(MDX_EINVAL, "%s: col_p=%ld must be in [0, coef_ld=%ld)", op, (long)d->col_p, (long)d->coef_ld);
     if (d->cfg != 0 && d->cfg != 1) return set_error(MDX_EINVAL, "%s: cfg=%ld must be 0 or 1", op, (long)d->cfg);
-    if (d->xin_ld > 0 && (d->xin_c <= 0 || d->xin_c > d->xin_ld || d->n % d->xin_c))
-        return set_error(MDX_EINVAL, "%s: xin_c=%ld must be in (0, xin_ld=%ld] and divide n=%ld", op, (long)d->xin_c, (long)d->xin_ld, (long)d->n);
+    MDX_NEED(need_xin(op, d));
     if (d->n == 0) return MDX_OK;
     const long bpg = (long)((d->group_elems + 3) / 4);           // blocks of four relative indices per group; the last may be partial
-    RenoiseParams p{d->x, d->x_in, d->coef, d->step_ptr, d->visit_ptr, (const unsigned long long*)d->seeds, d->n, d->group_elems, bpg,
-                    (int)d->jump, (int)d->n_rows, (int)d->coef_ld, (int)d->col_t, (int)d->col_p, (int)d->cfg, (int)d->xin_c, (int)d->xin_ld};
+    RenoiseParams p{d->x, d->coef, d->step_ptr, d->visit_ptr, (const unsigned long long*)d->seeds, d->group_elems, bpg,
+                    (int)d->jump, (int)d->n_rows, (int)d->coef_ld, (int)d->col_t, (int)d->col_p, xin_of(d)};
     const bool vec = ((uintptr_t)d->x & 15) == 0 && d->group_elems % 4 == 0;
-    const long work = (p.n / p.group) * bpg;
+    const long work = (d->n / p.group) * bpg;
     const long blocks = (work + RN_T - 1) / RN_T;
     if (blocks > 0x7fffffffL) return set_error(MDX_EINVAL, "%s: n=%ld needs more than 2^31 - 1 workgroups", op, (long)d->n);
     hipStream_t st = (hipStream_t)stream;

@@ -46,6 +46,42 @@ def _nhwc(t: torch.Tensor):
     return B, H, W, Cc, ld
 
 
+def _lower_xin(d, what: str, x_in: Optional[torch.Tensor], n: int, cfg: bool, xin_c: int):
+    """x_in / n / cfg / xin_c / xin_ld of a latent op's descriptor (csrc/latent.h: XinDst).  x_in holds the n latents once, twice under
+    CFG: fp32 flat, or 16-bit channels-last [pixels, ld] with xin_c channels per pixel and ld >= xin_c (padded); an fp32 or absent x_in
+    leaves xin_c = xin_ld = 0."""
+    c = 2 if cfg else 1
+    d.x_in, d.n, d.cfg = _p(x_in), n, int(cfg)
+    if x_in is None:
+        return
+    if x_in.dtype == F32:
+        _chk(x_in.is_contiguous() and x_in.numel() == c * n, f"{what}: fp32 x_in must hold {c} x n elements")
+    else:
+        _chk(x_in.dtype in H16 and x_in.dim() == 2 and x_in.is_contiguous() and xin_c > 0, f"{what}: 16-bit x_in must be [pixels, ld]")
+        _chk(x_in.shape[0] * xin_c == c * n and x_in.shape[1] >= xin_c, f"{what}: 16-bit x_in shape")
+        d.xin_c, d.xin_ld = xin_c, x_in.shape[1]
+
+
+def _lower_given_views(d, what: str, n: int, mode: int, mask, cond, noise, last_step: int):
+    """gv_* of a scheduler op's descriptor (MdxDdimDesc.gv_*): mask uint8 [views], cond / noise fp32 [n] in x's layout, mode 1 | 2."""
+    if not mode:
+        return
+    _chk(mode in (1, 2) and mask is not None and mask.dtype == torch.uint8 and mask.is_contiguous() and n % mask.numel() == 0, f"{what}: given-view mask")
+    _chk(noise is not None and noise.dtype == F32 and noise.is_contiguous() and noise.numel() == n, f"{what}: gv_noise")
+    _chk(mode == 2 or (cond is not None and cond.dtype == F32 and cond.is_contiguous() and cond.numel() == n), f"{what}: gv_cond")
+    d.gv_mask, d.gv_noise, d.gv_cond = _p(mask), _p(noise), _p(cond)
+    d.gv_mode, d.gv_view_elems, d.gv_last_step = mode, n // mask.numel(), last_step
+
+
+def _columns(what: str, table: dict, ld: int, cols, names: str):
+    """The two coefficient columns of a latent op: as given, or (either negative) by the table's width."""
+    if min(cols) < 0:
+        _chk(ld in table, f"{what}: a coefficient table of width {ld} needs {names}")
+        cols = table[ld]
+    _chk(all(0 <= c < ld for c in cols), f"{what}: columns {cols[0]}, {cols[1]} of a table of width {ld}")
+    return cols
+
+
 @dataclass
 class Gemm:
     """C = epi(A @ W^T + bias + temb[row]) + R.  A [M,K] or [Bt,M,K]; W [N,K] or [Bt,N,K]; C [M,No] or [Bt,M,No]."""
@@ -564,23 +600,9 @@ class DdimStep:
         _chk(self.x.is_contiguous() and self.eps.is_contiguous() and self.eps.numel() == n * (2 if self.cfg else 1), "ddim: sizes")
         _chk(self.x.dtype == F32 and self.eps.dtype == F32 and self.coef.dtype == F32 and self.step.dtype == torch.int32, "ddim: dtypes")
         d = L.MdxDdimDesc()
-        d.x, d.eps, d.coef, d.step_ptr, d.x_in = _p(self.x), _p(self.eps), _p(self.coef), _p(self.step), _p(self.x_in)
-        if self.x_in is not None:
-            if self.x_in.dtype == F32:
-                _chk(self.x_in.is_contiguous() and self.x_in.numel() == self.eps.numel(), "ddim: x_in")
-            else:
-                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.x_in.is_contiguous() and self.xin_c > 0, "ddim: bf16 x_in must be [pixels, ld]")
-                _chk(self.x_in.shape[0] * self.xin_c == self.eps.numel() and self.x_in.shape[1] >= self.xin_c, "ddim: bf16 x_in shape")
-                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
-        d.n, d.cfg, d.guidance = n, int(self.cfg), float(self.guidance)
-        if self.gv_mode:
-            _chk(self.gv_mode in (1, 2) and self.gv_mask is not None and self.gv_mask.dtype == torch.uint8 and self.gv_mask.is_contiguous()
-                 and n % self.gv_mask.numel() == 0, "ddim: given-view mask")
-            _chk(self.gv_noise is not None and self.gv_noise.dtype == F32 and self.gv_noise.is_contiguous() and self.gv_noise.numel() == n, "ddim: gv_noise")
-            _chk(self.gv_mode == 2 or (self.gv_cond is not None and self.gv_cond.dtype == F32 and self.gv_cond.is_contiguous()
-                                       and self.gv_cond.numel() == n), "ddim: gv_cond")
-            d.gv_mask, d.gv_noise, d.gv_cond = _p(self.gv_mask), _p(self.gv_noise), _p(self.gv_cond)
-            d.gv_mode, d.gv_view_elems, d.gv_last_step = self.gv_mode, n // self.gv_mask.numel(), self.gv_last_step
+        d.x, d.eps, d.coef, d.step_ptr, d.guidance = _p(self.x), _p(self.eps), _p(self.coef), _p(self.step), float(self.guidance)
+        _lower_xin(d, "ddim", self.x_in, n, self.cfg, self.xin_c)
+        _lower_given_views(d, "ddim", n, self.gv_mode, self.gv_mask, self.gv_cond, self.gv_noise, self.gv_last_step)
         return self.opcode, d
 
 
@@ -612,23 +634,10 @@ class UniPCStep:
         _chk(self.eps.numel() == n * (2 if self.cfg else 1) and all(t.numel() == n and t.dtype == F32 and t.is_contiguous() for t in (self.x, self.x_last, self.m1, self.m2)), "unipc: sizes")
         _chk(self.coef.dtype == F32 and self.coef.shape[1] == 12 and self.step.dtype == torch.int32, "unipc: coef/step")
         d = L.MdxUniPCDesc()
-        d.x, d.eps, d.coef, d.step_ptr, d.x_in = _p(self.x), _p(self.eps), _p(self.coef), _p(self.step), _p(self.x_in)
+        d.x, d.eps, d.coef, d.step_ptr, d.guidance = _p(self.x), _p(self.eps), _p(self.coef), _p(self.step), float(self.guidance)
         d.x_last, d.m1, d.m2 = _p(self.x_last), _p(self.m1), _p(self.m2)
-        if self.x_in is not None:
-            if self.x_in.dtype == F32:
-                _chk(self.x_in.numel() == self.eps.numel(), "unipc: x_in")
-            else:
-                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.xin_c > 0 and self.x_in.shape[0] * self.xin_c == self.eps.numel(), "unipc: bf16 x_in")
-                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
-        d.n, d.cfg, d.guidance = n, int(self.cfg), float(self.guidance)
-        if self.gv_mode:
-            _chk(self.gv_mode in (1, 2) and self.gv_mask is not None and self.gv_mask.dtype == torch.uint8 and self.gv_mask.is_contiguous()
-                 and n % self.gv_mask.numel() == 0, "unipc: given-view mask")
-            _chk(self.gv_noise is not None and self.gv_noise.dtype == F32 and self.gv_noise.is_contiguous() and self.gv_noise.numel() == n, "unipc: gv_noise")
-            _chk(self.gv_mode == 2 or (self.gv_cond is not None and self.gv_cond.dtype == F32 and self.gv_cond.is_contiguous()
-                                       and self.gv_cond.numel() == n), "unipc: gv_cond")
-            d.gv_mask, d.gv_noise, d.gv_cond = _p(self.gv_mask), _p(self.gv_noise), _p(self.gv_cond)
-            d.gv_mode, d.gv_view_elems, d.gv_last_step = self.gv_mode, n // self.gv_mask.numel(), self.gv_last_step
+        _lower_xin(d, "unipc", self.x_in, n, self.cfg, self.xin_c)
+        _lower_given_views(d, "unipc", n, self.gv_mode, self.gv_mask, self.gv_cond, self.gv_noise, self.gv_last_step)
         return self.opcode, d
 
 
@@ -745,23 +754,11 @@ class LatentBlend:
         _chk(self.coef.dtype == F32 and self.coef.dim() == 2 and self.coef.is_contiguous() and self.step.dtype == torch.int32 and self.step.numel() == 1,
              f"blend {self.name}: coef fp32 [steps, ld], step int32 [1]")
         ld = self.coef.shape[1]
-        col_a, col_s = self.col_a, self.col_s
-        if col_a < 0 or col_s < 0:
-            _chk(ld in self.COLUMNS, f"blend {self.name}: a coefficient table of width {ld} needs col_a / col_s")
-            col_a, col_s = self.COLUMNS[ld]
-        _chk(0 <= col_a < ld and 0 <= col_s < ld, f"blend {self.name}: columns {col_a}, {col_s} of a table of width {ld}")
+        col_a, col_s = _columns(f"blend {self.name}", self.COLUMNS, ld, (self.col_a, self.col_s), "col_a / col_s")
         d = L.MdxBlendDesc()
-        d.x, d.cond, d.noise, d.mask, d.coef, d.step_ptr, d.x_in = _p(self.x), _p(self.cond), _p(self.noise), _p(self.mask), _p(self.coef), _p(self.step), _p(self.x_in)
-        c = 2 if self.cfg else 1
-        if self.x_in is not None:
-            if self.x_in.dtype == F32:
-                _chk(self.x_in.is_contiguous() and self.x_in.numel() == c * n, f"blend {self.name}: fp32 x_in must hold {c} x n elements")
-            else:
-                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.x_in.is_contiguous() and self.xin_c > 0, f"blend {self.name}: 16-bit x_in must be [pixels, ld]")
-                _chk(self.x_in.shape[0] * self.xin_c == c * n and self.x_in.shape[1] >= self.xin_c, f"blend {self.name}: 16-bit x_in shape")
-                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
-        d.n, d.mask_elems, d.coef_ld, d.col_a, d.col_s = n, n // self.mask.numel(), ld, col_a, col_s
-        d.last_step, d.cfg = int(self.last_step), int(self.cfg)
+        d.x, d.cond, d.noise, d.mask, d.coef, d.step_ptr = _p(self.x), _p(self.cond), _p(self.noise), _p(self.mask), _p(self.coef), _p(self.step)
+        _lower_xin(d, f"blend {self.name}", self.x_in, n, self.cfg, self.xin_c)
+        d.mask_elems, d.coef_ld, d.col_a, d.col_s, d.last_step = n // self.mask.numel(), ld, col_a, col_s, int(self.last_step)
         return self.opcode, d
 
 
@@ -800,23 +797,11 @@ class LatentRenoise:
         _chk(all(t.dtype == torch.int32 and t.numel() == 1 for t in (self.step, self.visit)), f"renoise {self.name}: step and visit int32 [1]")
         _chk(isinstance(self.jump, int) and not isinstance(self.jump, bool) and self.jump >= 1, f"renoise {self.name}: jump={self.jump!r} must be an integer >= 1")
         ld = self.coef.shape[1]
-        col_t, col_p = self.col_t, self.col_p
-        if col_t < 0 or col_p < 0:
-            _chk(ld in self.COLUMNS, f"renoise {self.name}: a coefficient table of width {ld} needs col_t / col_p")
-            col_t, col_p = self.COLUMNS[ld]
-        _chk(0 <= col_t < ld and 0 <= col_p < ld, f"renoise {self.name}: columns {col_t}, {col_p} of a table of width {ld}")
+        col_t, col_p = _columns(f"renoise {self.name}", self.COLUMNS, ld, (self.col_t, self.col_p), "col_t / col_p")
         d = L.MdxRenoiseDesc()
-        d.x, d.x_in, d.coef, d.step_ptr, d.visit_ptr, d.seeds = _p(self.x), _p(self.x_in), _p(self.coef), _p(self.step), _p(self.visit), _p(self.seeds)
-        c = 2 if self.cfg else 1
-        if self.x_in is not None:
-            if self.x_in.dtype == F32:
-                _chk(self.x_in.is_contiguous() and self.x_in.numel() == c * n, f"renoise {self.name}: fp32 x_in must hold {c} x n elements")
-            else:
-                _chk(self.x_in.dtype in H16 and self.x_in.dim() == 2 and self.x_in.is_contiguous() and self.xin_c > 0, f"renoise {self.name}: 16-bit x_in must be [pixels, ld]")
-                _chk(self.x_in.shape[0] * self.xin_c == c * n and self.x_in.shape[1] >= self.xin_c, f"renoise {self.name}: 16-bit x_in shape")
-                d.xin_c, d.xin_ld = self.xin_c, self.x_in.shape[1]
-        d.n, d.group_elems, d.jump, d.n_rows, d.coef_ld, d.col_t, d.col_p = n, n // self.seeds.numel(), self.jump, self.coef.shape[0], ld, col_t, col_p
-        d.cfg = int(self.cfg)
+        d.x, d.coef, d.step_ptr, d.visit_ptr, d.seeds = _p(self.x), _p(self.coef), _p(self.step), _p(self.visit), _p(self.seeds)
+        _lower_xin(d, f"renoise {self.name}", self.x_in, n, self.cfg, self.xin_c)
+        d.group_elems, d.jump, d.n_rows, d.coef_ld, d.col_t, d.col_p = n // self.seeds.numel(), self.jump, self.coef.shape[0], ld, col_t, col_p
         return self.opcode, d
 
 

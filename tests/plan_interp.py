@@ -182,61 +182,62 @@ def run_timeemb(op: O.TimeEmb):
     op.Y.copy_(emb)
 
 
-def run_ddim(op: O.DdimStep):
-    n = op.x.numel()
-    c = op.coef[int(op.step.item())]
+def _guided_eps(op, n):
+    """eps after the CFG combine, with a given view's own noise in its place under gv_mode 2 -> (eps, given-element mask or None)."""
     e = op.eps[:n] + op.guidance * (op.eps[n:] - op.eps[:n]) if op.cfg else op.eps
     given = None
     if op.gv_mode:
         given = op.gv_mask.bool().repeat_interleave(n // op.gv_mask.numel())
         if op.gv_mode == 2:
             e = torch.where(given, op.gv_noise, e)
-    x0 = (op.x - c[1] * e) / c[0]
-    xn = c[2] * x0 + c[3] * e
+    return e, given
+
+
+def _renoise_given(op, given, a, s, xn):
+    """gv_mode 1: below gv_last_step a given element leaves the step as a * cond + s * noise."""
     if op.gv_mode == 1 and int(op.step.item()) < op.gv_last_step:
-        xn = torch.where(given, c[2] * op.gv_cond + c[3] * op.gv_noise, xn)
+        xn = torch.where(given, a * op.gv_cond + s * op.gv_noise, xn)
+    return xn
+
+
+def _refresh_x_in(op, xn):
+    """The model-input copy of the new latents: fp32 flat or 16-bit [pixels, ld] (pad channels untouched), both halves under CFG."""
+    if op.x_in is None:
+        return
+    n = xn.numel()
+    if op.x_in.dtype == torch.float32:
+        op.x_in[:n].copy_(xn)
+        if op.cfg:
+            op.x_in[n:].copy_(xn)
+    else:
+        npx = n // op.xin_c
+        v = xn.view(npx, op.xin_c).to(op.x_in.dtype)
+        op.x_in[:npx, :op.xin_c].copy_(v)
+        if op.cfg:
+            op.x_in[npx:, :op.xin_c].copy_(v)
+
+
+def run_ddim(op: O.DdimStep):
+    n = op.x.numel()
+    c = op.coef[int(op.step.item())]
+    e, given = _guided_eps(op, n)
+    x0 = (op.x - c[1] * e) / c[0]
+    xn = _renoise_given(op, given, c[2], c[3], c[2] * x0 + c[3] * e)
     op.x.copy_(xn)
-    if op.x_in is not None:
-        if op.x_in.dtype == torch.float32:
-            op.x_in[:n].copy_(xn)
-            if op.cfg:
-                op.x_in[n:].copy_(xn)
-        else:
-            npx = n // op.xin_c
-            v = xn.view(npx, op.xin_c).to(op.x_in.dtype)
-            op.x_in[:npx, :op.xin_c].copy_(v)
-            if op.cfg:
-                op.x_in[npx:, :op.xin_c].copy_(v)
+    _refresh_x_in(op, xn)
     op.step += 1
 
 
 def run_unipc(op: O.UniPCStep):
     n = op.x.numel()
     c = op.coef[int(op.step.item())]
-    e = op.eps[:n] + op.guidance * (op.eps[n:] - op.eps[:n]) if op.cfg else op.eps
-    given = None
-    if op.gv_mode:
-        given = op.gv_mask.bool().repeat_interleave(n // op.gv_mask.numel())
-        if op.gv_mode == 2:
-            e = torch.where(given, op.gv_noise, e)
+    e, given = _guided_eps(op, n)
     x = op.x.clone(); m1 = op.m1.clone(); m2 = op.m2.clone()
     mt = c[0] * x + c[1] * e
     xc = c[3] * op.x_last + c[4] * m1 + c[5] * m2 + c[6] * mt if c[2] != 0 else x
-    xn = c[7] * xc + c[8] * mt + c[9] * m1
-    if op.gv_mode == 1 and int(op.step.item()) < op.gv_last_step:
-        xn = torch.where(given, c[10] * op.gv_cond + c[11] * op.gv_noise, xn)
+    xn = _renoise_given(op, given, c[10], c[11], c[7] * xc + c[8] * mt + c[9] * m1)
     op.x.copy_(xn); op.x_last.copy_(xc); op.m2.copy_(m1); op.m1.copy_(mt)
-    if op.x_in is not None:
-        if op.x_in.dtype == torch.float32:
-            op.x_in[:n].copy_(xn)
-            if op.cfg:
-                op.x_in[n:].copy_(xn)
-        else:
-            npx = n // op.xin_c
-            v = xn.view(npx, op.xin_c).to(op.x_in.dtype)
-            op.x_in[:npx, :op.xin_c].copy_(v)
-            if op.cfg:
-                op.x_in[npx:, :op.xin_c].copy_(v)
+    _refresh_x_in(op, xn)
     op.step += 1
 
 

@@ -76,8 +76,8 @@ CONSTANTS = {          # key: (value, "file:line[-line]", text that must stand o
     "ln.lanes": (64, "norm.hip:374", "lane + 64 * i"),
     "ln.MAXV": (4, "norm.hip:574", "layernorm_kernel<4, 1, AFFINE>"),
     "softmax.lanes": (64, "norm.hip:546", "c += 64"),
-    "ew.vec": (8, "elementwise.hip:580", "p.C % 8 == 0"),
-    "ew.block": (256, "elementwise.hip:227", "__launch_bounds__(256) void ew_scalar_kernel"),
+    "ew.vec": (8, "elementwise.hip:539", "p.C % 8 == 0"),
+    "ew.block": (256, "elementwise.hip:228", "__launch_bounds__(256) void ew_scalar_kernel"),
 }
 
 
@@ -627,7 +627,7 @@ def _norm_hits(c, family):
     return {("C", c["C"]), ("HW", c["H"] * c["W"])}
 
 
-# ---- direct conv: the three kernels of elementwise.hip:531-551 ----
+# ---- direct conv: the three kernels of elementwise.hip:490-510 ----
 DIRECT_COUT = (1, 2, 3, 4, 5, 8, 9)
 DIRECT_CIN = (4, 64, 128, 320, 336, 344)
 DIRECT_WS_M = (65536, 65537, 65551, 65599)
@@ -635,7 +635,7 @@ DIRECT_LINEAR_K = (189, 216)
 
 
 def direct_tag(c):
-    """elementwise.hip:531-551: K-parallel from K >= 512 with Cout <= 8 and 16-byte channel rows; weight-stationary with Cout <= 4, at most
+    """elementwise.hip:490-510: K-parallel from K >= 512 with Cout <= 8 and 16-byte channel rows; weight-stationary with Cout <= 4, at most
     384 (tap, 8-channel) chunks and M >= 65536."""
     kpar = c["Cout"] <= 8 and c["Cin"] % 8 == 0 and c["K"] >= 512
     if kpar and c["Cout"] <= 4 and c["k"] * c["k"] * (c["Cin"] // 8) <= 384 and c["M"] >= 65536:
@@ -739,7 +739,7 @@ def _steps_hits(c, step):
     return {("narrow", C)} if C % 8 else {("C", C), ("M", c["M"], C)}
 
 
-# ---- Fourier embedding, gather, timestep embedding, the DDIM step (elementwise.hip:326-460: one thread per output element / feature) ----
+# ---- Fourier embedding, gather, timestep embedding, the DDIM step (elementwise.hip:327-455: one thread per output element / feature) ----
 MISC_N = (1, 63, 65)
 FOURIER_F = (0, 1, 16)
 DDIM_N = (1, 3, 255, 256, 257, 1025)

@@ -321,6 +321,13 @@ TABLE += [
 TABLE += [
     (L.OP_GEMM, "Vt: A (M * lda * 2 bytes) below 0x7FFF0000", gemm(M=3355520, N=256, K=320, lda=320, ldw=320, ldc=128, Vt=P(5), vt_from=128, vt_T=8, vt_ld=8, vt_stride=1024),
      EINVAL, "2 GiB buffer window"),
+    # the x_in clauses every latent op shares (csrc/latent.h: need_xin; tests/test_xin_contract.py has the whole table for all four ops)
+    (L.OP_DDIM, "xin_ld is not negative", ddim(x_in=P(5), xin_ld=-8, xin_c=4), EINVAL, "xin_ld=-8"),
+    (L.OP_DDIM, "x_in at its element's alignment (4 / 2 bytes)", ddim(x_in=P(5) + 1, xin_ld=8, xin_c=4), EINVAL, "x_in must be 2-byte"),
+    (L.OP_DDIM, "x_in at its element's alignment (4 / 2 bytes)", ddim(x_in=P(5) + 2), EINVAL, "x_in must be 4-byte"),
+    (L.OP_UNIPC, "xin_ld is not negative", unipc(x_in=P(8), xin_ld=-8, xin_c=4), EINVAL, "xin_ld=-8"),
+    (L.OP_UNIPC, "x_in at its element's alignment (4 / 2 bytes)", unipc(x_in=P(8) + 1, xin_ld=8, xin_c=4), EINVAL, "x_in must be 2-byte"),
+    (L.OP_UNIPC, "x_in at its element's alignment (4 / 2 bytes)", unipc(x_in=P(8) + 2), EINVAL, "x_in must be 4-byte"),
 ]
 
 
@@ -361,6 +368,21 @@ def test_every_entry_point_has_rows():
     assert {op for op, *_ in TABLE} == set(L.DESC_OF_OP)
 
 
+def latent_helper_bodies():
+    """{name: body} of the host checks csrc/latent.h shares among the latent ops' entry points (need_xin, need_given_views)."""
+    import os
+    import re
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "magicdrive_amd", "csrc", "latent.h")).read()
+    bodies = dict(re.findall(r"template <class D> int (need_\w+)\(const char\* op, const D\* d\) \{\n(.*?)\n\}", hdr, re.S))
+    assert set(bodies) == {"need_xin", "need_given_views"}, sorted(bodies)
+    return bodies
+
+
+def with_latent_helpers(body):
+    """An entry point's body plus the body of each shared helper of csrc/latent.h that it calls."""
+    return body + "".join("\n" + hb for name, hb in latent_helper_bodies().items() if name + "(" in body)
+
+
 def _host_checks():
     """(entry point, field) of every need_int / need_multiple / need_aligned call with a literal field name in the entry points' sources."""
     import os
@@ -371,11 +393,12 @@ def _host_checks():
         parts = re.split(r'extern "C" int (mdx_\w+)\(', open(os.path.join(csrc, fn)).read())
         shared = re.findall(r'need_\w+\(op, "([^"]+)"', parts[0])          # helpers ahead of the first entry point (check_epilogue_operands)
         for name, body in zip(parts[1::2], parts[2::2]):
-            body = body.split("\nnamespace mdx {")[0]
+            body = with_latent_helpers(body.split("\nnamespace mdx {")[0])
             fields = re.findall(r'need_\w+\((?:op|"mdx_\w+"), "([^"]+)"', body)
             if "check_epilogue_operands(" in body:
                 fields += shared
             found |= {(name, f) for f in fields}
+    assert {(e, f) for e in ("mdx_cfg_ddim_step", "mdx_cfg_unipc_step") for f in ("x_in", "xin_c", "xin_ld")} <= found
     return found
 
 

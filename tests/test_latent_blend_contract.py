@@ -122,9 +122,11 @@ def test_an_empty_problem_is_still_checked():
 
 
 def test_every_host_check_has_a_row():
-    """Every field a check of the entry point names is named by a row, and every sentence the table quotes stands in the header."""
+    """Every field a check of the entry point (or of a shared helper of csrc/latent.h it calls) names is named by a row, and every sentence
+    the table quotes stands in the header."""
+    from test_contract import with_latent_helpers
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    body = open(os.path.join(root, "magicdrive_amd", "csrc", "blend.hip")).read().split('extern "C" int mdx_latent_blend_bf16(')[1]
+    body = with_latent_helpers(open(os.path.join(root, "magicdrive_amd", "csrc", "blend.hip")).read().split('extern "C" int mdx_latent_blend_bf16(')[1])
     fields = set(re.findall(r'need_\w+\(op, "([A-Za-z_]+)"', body)) | set(re.findall(r'"%s: (\w+)=%ld', body)) | set(re.findall(r'"%s: (\w+) must not be NULL"', body))
     assert fields == {"x", "cond", "noise", "mask", "coef", "step_ptr", "x_in", "n", "mask_elems", "coef_ld", "col_a", "col_s", "last_step", "cfg",
                       "xin_c", "xin_ld"}, fields

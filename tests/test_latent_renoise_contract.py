@@ -233,8 +233,10 @@ def test_an_empty_problem_is_still_checked():
 
 
 def test_every_host_check_has_a_row():
-    """Every field a check of the entry point names is named by a row, and every sentence the table quotes stands in the header."""
-    body = open(os.path.join(ROOT, "magicdrive_amd", "csrc", "noise.hip")).read().split('extern "C" int mdx_latent_renoise_bf16(')[1]
+    """Every field a check of the entry point (or of a shared helper of csrc/latent.h it calls) names is named by a row, and every sentence
+    the table quotes stands in the header."""
+    from test_contract import with_latent_helpers
+    body = with_latent_helpers(open(os.path.join(ROOT, "magicdrive_amd", "csrc", "noise.hip")).read().split('extern "C" int mdx_latent_renoise_bf16(')[1])
     fields = set(re.findall(r'need_\w+\(op, "([A-Za-z_]+)"', body)) | set(re.findall(r'"%s: (\w+)=%ld', body)) | set(re.findall(r'"%s: (\w+) must not be NULL"', body))
     assert fields == {"x", "x_in", "coef", "step_ptr", "visit_ptr", "seeds", "n", "group_elems", "jump", "n_rows", "coef_ld", "col_t", "col_p", "cfg",
                       "xin_c", "xin_ld"}, fields
