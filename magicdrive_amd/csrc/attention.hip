@@ -26,7 +26,7 @@
 #include "common.h"
 #include "launch.h"
 #include "options.h"
-#include "attn2.h"
+#include "attn.h"
 
 namespace mdx {
 
@@ -328,7 +328,7 @@ __global__ __launch_bounds__(NW * 64) void attn_kernel(AttnParams p) {
 }
 
 template <int D16, int NW>
-static int launch_attn(const AttnParams& p, hipStream_t st) {
+static int launch_attn(const AttnParams& p, const char* tag, hipStream_t st) {
     AttnParams q = p;
     const int qblocks = (p.Tq + NW * 32 - 1) / (NW * 32);
     const int swz = (int)opt(OPT_ATTN_SWZ);
@@ -341,89 +341,60 @@ static int launch_attn(const AttnParams& p, hipStream_t st) {
         grid = q.viewmap ? dim3((unsigned)(((long)p.B + 7) / 8 * 8 * p.H * qblocks), 1, 1)
                          : dim3((unsigned)(((long)p.B * p.H + 7) / 8 * 8 * qblocks), 1, 1);
     }
-    const bool two = p.nsrc == 2 && !p.joint;
-    if (two)
+    if (p.nsrc == 2 && !p.joint)
         hipLaunchKernelGGL((attn_kernel<D16, NW, true>), grid, dim3(NW * 64), 0, st, q);
     else
         hipLaunchKernelGGL((attn_kernel<D16, NW, false>), grid, dim3(NW * 64), 0, st, q);
-    char tag[64];
-    snprintf(tag, sizeof tag, "attn_kernel<%d,%d,%s>", D16, NW, two ? "xview" : (p.nsrc > 1 ? "joint" : "self"));
     return check_launch(tag);
 }
 
-template <int D16>
-static int launch_attn_nw(const AttnParams& p, hipStream_t st) {
-    // 4 waves (128 queries) per workgroup whenever (batch x heads) alone fills the chip — also for 91- and 28-token sequences: every
-    // thread of the workgroup stages K / V^T, so the idle query rows cost less than narrower workgroups lose on staging (384 views,
-    // T = 91, d = 160: 4 waves 103 us, 2 waves 152 us, 1 wave 448 us; T = 28: 39 / 44 / 71 us; cross-view at T = 28: 2 waves 73 vs 108 us).
-    // With few (batch, head) pairs the sequence is split finer so that short sequences still spread over the chip.
-    long blocks4 = (long)((p.Tq + 127) / 128) * p.H * p.B;
-    const long thr4 = (long)opt(OPT_ATTN_NW4_BLOCKS);
-    const long thr8 = (long)opt(OPT_ATTN_NW8_BLOCKS);
-    long blocks8 = (long)((p.Tq + 255) / 256) * p.H * p.B;
-    const int force = (int)opt(OPT_ATTN_NW);     // experiments: force 1 / 2 / 4 / 8 waves
-    if (force == 8) return launch_attn<D16, 8>(p, st);
-    if (force == 4) return launch_attn<D16, 4>(p, st);
-    if (force == 2) return launch_attn<D16, 2>(p, st);
-    if (force == 1) return launch_attn<D16, 1>(p, st);
-    if (p.Tq >= 512 && blocks8 >= thr8) return launch_attn<D16, 8>(p, st);
-    if (p.Tq >= 256 && blocks4 >= thr4) return launch_attn<D16, 4>(p, st);
-    if ((long)p.H * p.B >= 2 * thr4) return (p.Tq <= 32 && p.nsrc == 2) ? launch_attn<D16, 2>(p, st) : launch_attn<D16, 4>(p, st);
-    if (p.Tq >= 64) return launch_attn<D16, 2>(p, st);
-    return launch_attn<D16, 1>(p, st);
+template <int D16>       // nw: the waves per workgroup attn_route.h chose (attn_waves)
+static int launch_attn_nw(const AttnParams& p, int nw, const char* tag, hipStream_t st) {
+    return nw == 8 ? launch_attn<D16, 8>(p, tag, st) : nw == 4 ? launch_attn<D16, 4>(p, tag, st) : nw == 2 ? launch_attn<D16, 2>(p, tag, st) : launch_attn<D16, 1>(p, tag, st);
 }
 
 }  // namespace mdx
 
 using namespace mdx;
 
+// THE attention entry point (mdx_attention_f16 in the fp16 build: launch.h).  attn_route.h names the family: the context and the short route
+// run their own host checks (attention_ctx.hip, attention_short.hip); the instances of attention2.hip and of this file share the ones below.
 extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
+    const mdx_route::AttnFamily fam = a ? mdx_route::attn_family(attn_in(a)) : mdx_route::ATTN_FLASH;
+    hipStream_t st = (hipStream_t)stream;
+    if (fam == mdx_route::ATTN_CTX) return attn_ctx(a, st, MDX_F16 ? "mdx_attention_f16" : "mdx_attention_bf16", false);
+    if (fam == mdx_route::ATTN_SHORT) return attn_short(a, st, MDX_F16 ? "mdx_attention_f16" : "mdx_attention_bf16");
     if (!a || !a->Q || !a->K || !a->Vt || !a->O) return set_error(MDX_EINVAL, "mdx_attention_bf16: null operand");
     const char* op = "mdx_attention_bf16";
     if (a->d % 8 || a->d <= 0 || a->d > 160) return set_error(MDX_EINVAL, "head dim d=%ld unsupported (d %% 8 == 0, d <= 160)", (long)a->d);
-    {   // kernel instances exist for 1-6, 8 and 10 chunks of 16 columns (a ragged last chunk is masked): d in (96, 112] and (128, 144] has none
-        const int d16 = (int)(a->d + 15) / 16;
-        if (d16 == 7 || d16 == 9) return set_error(MDX_EUNSUPPORTED, "head dim d=%ld: no kernel instance (d/16 = %d)", (long)a->d, d16);
-    }
+    // kernel instances exist for 1-6, 8 and 10 chunks of 16 columns (a ragged last chunk is masked): d in (96, 112] and (128, 144] has none
+    if (const int d16 = (int)(a->d + 15) / 16; d16 == 7 || d16 == 9) return set_error(MDX_EUNSUPPORTED, "head dim d=%ld: no kernel instance (d/16 = %d)", (long)a->d, d16);
     if (a->joint != 0 && a->joint != 1) return set_error(MDX_EINVAL, "joint must be 0 or 1");
     if (a->nsrc < 1 || a->nsrc > (a->joint ? 8 : 2)) return set_error(MDX_EINVAL, "nsrc must be 1 or 2 (joint: 1..8)");
     if (a->nsrc > 1 && !a->kvmap) return set_error(MDX_EINVAL, "nsrc > 1 needs a kvmap");
-    MDX_NEED(need_int(op, "B", a->B)); MDX_NEED(need_int(op, "H", a->H)); MDX_NEED(need_int(op, "Tq", a->Tq)); MDX_NEED(need_int(op, "Tk", a->Tk));
-    // Q / K rows and V^T rows are read as 16-byte pieces; an O row is written as 8-byte pieces (4 head-dim columns of one query)
-    MDX_NEED(need_multiple(op, "ldq", a->ldq, 8)); MDX_NEED(need_multiple(op, "ldk", a->ldk, 8)); MDX_NEED(need_multiple(op, "ldv", a->ldv, 8));
-    MDX_NEED(need_multiple(op, "sQ", a->sQ, 8)); MDX_NEED(need_multiple(op, "sK", a->sK, 8)); MDX_NEED(need_multiple(op, "sV", a->sV, 8));
-    MDX_NEED(need_multiple(op, "ldo", a->ldo, 4)); MDX_NEED(need_multiple(op, "sO", a->sO, 4));
-    MDX_NEED(need_aligned(op, "Q", a->Q, 16)); MDX_NEED(need_aligned(op, "K", a->K, 16)); MDX_NEED(need_aligned(op, "Vt", a->Vt, 16));
-    MDX_NEED(need_aligned(op, "O", a->O, 8)); MDX_NEED(need_aligned(op, "kvmap", a->kvmap, 4));
+    MDX_NEED(need_attn_layout(op, a)); MDX_NEED(need_aligned(op, "kvmap", a->kvmap, 4));
     if (a->q_prescaled != 0 && a->q_prescaled != 1) return set_error(MDX_EINVAL, "q_prescaled must be 0 or 1");
     if (a->Tk > 0 && a->ldv < a->Tk) return set_error(MDX_EINVAL, "ldv < Tk");
     if (a->Tq <= 0 || a->Tk <= 0 || a->B <= 0 || a->H <= 0) return MDX_OK;
-    AttnParams p;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.Vt = (const bf16_t*)a->Vt; p.O = (bf16_t*)a->O;
-    p.kvmap = a->kvmap;
-    p.B = (int)a->B; p.H = (int)a->H; p.Tq = (int)a->Tq; p.Tk = (int)a->Tk; p.d = (int)a->d; p.nsrc = (int)a->nsrc; p.joint = (int)a->joint;
-    p.ldq = a->ldq; p.sQ = a->sQ; p.ldk = a->ldk; p.sK = a->sK; p.ldv = a->ldv; p.sV = a->sV; p.ldo = a->ldo; p.sO = a->sO;
-    // q_prescaled: the caller folded scale * log2(e) into the query projection: scores are base-2 exponents already
-    p.scale_log2 = a->q_prescaled ? 1.0f : (float)(a->scale * 1.4426950408889634);
-    hipStream_t st = (hipStream_t)stream;
-    {
+    char tag[64];
+    const AttnRoute r = attn_route_of(a, false, tag);
+    if (r.family != mdx_route::ATTN_FLASH) {
         Attn2Params p2;
-        p2.Q = p.Q; p2.K = p.K; p2.Vt = p.Vt; p2.O = p.O; p2.kvmap = p.kvmap;
-        p2.B = p.B; p2.H = p.H; p2.Tq = p.Tq; p2.Tk = p.Tk; p2.d = p.d; p2.nsrc = p.nsrc; p2.joint = p.joint;
-        p2.ldq = p.ldq; p2.sQ = p.sQ; p2.ldk = p.ldk; p2.sK = p.sK; p2.ldv = p.ldv; p2.sV = p.sV; p2.ldo = p.ldo; p2.sO = p.sO;
-        p2.scale_log2 = p.scale_log2; p2.qblocks = 0; p2.q_prescaled = (int)a->q_prescaled;
-        if (attn2_supported(p2)) return launch_attn2(p2, st);
+        fill_attn_sources(p2, a);
+        p2.qblocks = 0; p2.q_prescaled = (int)a->q_prescaled;
+        return launch_attn2(p2, r, tag, st);
     }
-    int d16 = (int)(a->d + 15) / 16;
-    switch (d16) {
-        case 1: return launch_attn_nw<1>(p, st);
-        case 2: return launch_attn_nw<2>(p, st);
-        case 3: return launch_attn_nw<3>(p, st);
-        case 4: return launch_attn_nw<4>(p, st);
-        case 5: return launch_attn_nw<5>(p, st);
-        case 6: return launch_attn_nw<6>(p, st);
-        case 8: return launch_attn_nw<8>(p, st);
-        case 10: return launch_attn_nw<10>(p, st);
-        default: return set_error(MDX_EUNSUPPORTED, "head dim %ld: no kernel instance (d/16 = %d)", (long)a->d, d16);
+    AttnParams p;
+    fill_attn_sources(p, a);
+    switch (r.d16) {
+        case 1: return launch_attn_nw<1>(p, r.nw, tag, st);
+        case 2: return launch_attn_nw<2>(p, r.nw, tag, st);
+        case 3: return launch_attn_nw<3>(p, r.nw, tag, st);
+        case 4: return launch_attn_nw<4>(p, r.nw, tag, st);
+        case 5: return launch_attn_nw<5>(p, r.nw, tag, st);
+        case 6: return launch_attn_nw<6>(p, r.nw, tag, st);
+        case 8: return launch_attn_nw<8>(p, r.nw, tag, st);
+        case 10: return launch_attn_nw<10>(p, r.nw, tag, st);
+        default: return set_error(MDX_EUNSUPPORTED, "head dim %ld: no kernel instance (d/16 = %d)", (long)a->d, r.d16);
     }
 }

@@ -25,7 +25,7 @@
 #include "launch.h"
 #include "options.h"
 #include "xl_layout.h"
-#include "attn2.h"
+#include "attn.h"
 #include "attn3_layout.h"
 
 namespace mdx {
@@ -766,75 +766,32 @@ __global__ __launch_bounds__(A2_NT, (QT == 2 || D8 > 5) ? 2 : ((RES || (A2_LB4_T
         }
 }
 
-// resident K / V^T (attn2_kernel<.., RES>): one workgroup per (batch, head)
-template <int D8, bool FOLD>
-static int launch_attn2_res(const Attn2Params& p, hipStream_t st) {
+// RES: resident K / V^T (attn2_kernel<.., RES>), one workgroup per (batch, head) walks the query blocks
+template <int D8, int QT, bool FOLD, bool PF = false, bool RES = false>
+static int launch_attn2_d(const Attn2Params& p, const char* tag, hipStream_t st) {
     Attn2Params q = p;
-    q.qblocks = 1;
-    q.viewmap = opt(OPT_ATTN2_VIEWMAP) != 0;
-    const dim3 grid(q.viewmap ? (unsigned)(((long)p.B + 7) / 8 * 8 * p.H) : (unsigned)(((long)p.B * p.H + 7) / 8 * 8), 1, 1);
-    hipLaunchKernelGGL((attn2_kernel<D8, false, 1, FOLD, true>), grid, dim3(A2_NT), 0, st, q);
-    char tag[64];
-    snprintf(tag, sizeof tag, "attn2_kernel<%d,resident,q32%s>", D8 * 8, FOLD ? ",fold" : "");
-    return check_launch(tag);
-}
-
-template <int D8, int QT, bool FOLD, bool PF = false>
-static int launch_attn2_d(const Attn2Params& p, hipStream_t st) {
-    Attn2Params q = p;
-    q.qblocks = (p.Tq + A2_NW * 32 * QT - 1) / (A2_NW * 32 * QT);
+    q.qblocks = RES ? 1 : (p.Tq + A2_NW * 32 * QT - 1) / (A2_NW * 32 * QT);
     q.viewmap = opt(OPT_ATTN2_VIEWMAP) != 0;
     const dim3 grid(q.viewmap ? (unsigned)(((long)p.B + 7) / 8 * 8 * p.H * q.qblocks) : (unsigned)(((long)p.B * p.H + 7) / 8 * 8 * q.qblocks), 1, 1);
-    const bool two = p.nsrc == 2 && !p.joint;                   // TWO = the summed two-neighbour form; everything else is one softmax over nsrc sources
-    if (two) hipLaunchKernelGGL((attn2_kernel<D8, true, QT, FOLD, false, PF>), grid, dim3(A2_NT), 0, st, q);
+    if constexpr (RES) hipLaunchKernelGGL((attn2_kernel<D8, false, 1, FOLD, true>), grid, dim3(A2_NT), 0, st, q);
+    else if (p.nsrc == 2 && !p.joint)                           // TWO = the summed two-neighbour form; everything else is one softmax over nsrc sources
+        hipLaunchKernelGGL((attn2_kernel<D8, true, QT, FOLD, false, PF>), grid, dim3(A2_NT), 0, st, q);
     else hipLaunchKernelGGL((attn2_kernel<D8, false, QT, FOLD, false, PF>), grid, dim3(A2_NT), 0, st, q);
-    char tag[64];
-    snprintf(tag, sizeof tag, "attn2_kernel<%d,%s,q%d%s%s>", D8 * 8, two ? "xview" : (p.nsrc > 1 ? "joint" : "self"), 32 * QT, FOLD ? ",fold" : "", PF ? ",pf" : "");
     return check_launch(tag);
 }
 
-// Shapes the lean kernel takes (everything else stays on attention.hip): head dim 40 or 80, enough query blocks to fill the chip,
-// 16-byte aligned K rows / V^T rows, matrices within the 2 GiB DMA window.
-bool attn2_supported(const Attn2Params& p) {
-    const int on = (int)opt(OPT_ATTN2);
-    // d = 80 (level 1, T = 350): 0 never, 1 always, 2 (default) only the two-source cross-view form — measured at 768 views with the
-    // round-4 issue path (profiles/r04_attn_d80.log): cross-view 923 vs 1000-1012 us on attention.hip, self 545 vs 517-529 us
-    const int d80 = (int)opt(OPT_ATTN2_D80);
-    const bool xview2 = p.nsrc == 2 && !p.joint;
-    if (!on || (p.d != 40 && !(p.d == 80 && (d80 == 1 || (d80 == 2 && xview2))))) return false;
-    if (p.Tq < 256 || (long)((p.Tq + 127) / 128) * p.H * p.B < 128) return false;
-    if ((p.ldk % 8) || (p.ldv % 8) || (p.sK % 8) || (p.sV % 8) || (p.ldv < ((p.Tk + 7) / 8) * 8)) return false;
-    if ((long)p.Tk * p.ldk * 2 >= 0x40000000L || (long)p.d * p.H * p.ldv * 2 >= 0x40000000L) return false;
-    return true;
-}
+static_assert(A2_KV == mdx_route::A2_KV_TILE && A2_NBUF == mdx_route::A2_RES_TILES, "attn_route.h sizes the resident form by this file's tile and ring");
 
-int launch_attn2(const Attn2Params& p, hipStream_t st) {
-    // 64 queries per wave (see attn2_kernel) when there are enough queries per head; MDX_ATTN2_QT=1 forces 32
-    const int qt_opt = (int)opt(OPT_ATTN2_QT);          // 0 (default): 64-query waves except where the 32-query FOLD form wins; 1 / 2: force
-    const int qt = qt_opt == 0 ? 2 : qt_opt;
-    const bool qt_forced64 = qt_opt == 2;
-    const bool two = qt == 2 && p.Tq >= 512 && p.d == 40;
-    // pre-scaled Q (scale * log2 e folded into to_q at pack time): scores are base-2 exponents as they come out of the MFMA
-    const bool fold = p.q_prescaled && opt(OPT_ATTN2_FOLD) != 0;
-    // short kv sequences (the text context): every tile resident in the ring, one workgroup per (batch, head) walks the query blocks
-    // (ATTN2_RES: 1 = when the launch has enough (batch, head) pairs to fill the chip on its own and several query blocks to walk; 2 = whenever supported)
-    const int res_opt = (int)opt(OPT_ATTN2_RES);
-    if (p.d == 40 && fold && p.nsrc == 1 && (p.Tk + A2_KV - 1) / A2_KV <= A2_NBUF &&
-        (res_opt == 2 || (res_opt == 1 && p.Tq >= 512 && (long)p.B * p.H >= 1024)))
-        return launch_attn2_res<5, true>(p, st);
+// Executes the instance attn_route.h chose (attn2_supported and the rules behind it live there).
+int launch_attn2(const Attn2Params& p, const AttnRoute& r, const char* tag, hipStream_t st) {
+    if (r.family == mdx_route::ATTN2_RESIDENT) return launch_attn2_d<5, 1, true, false, true>(p, tag, st);
 #ifdef MDX_ATTN3                                                  // tools/attn3/attention3.hip, only in `make ATTN3=1` builds (round 6: out of the product library)
     if (attn3_supported(p)) return launch_attn3(p, st);          // round 5: the software-pipelined, permute-free form
 #endif
-    if (p.d == 40) {
-        // FOLD frees the registers / VALU slots of the scale-and-subtract: with it the 32-query form (<= 142 VGPRs: three waves per SIMD)
-        // is the faster one for one kv source (768 views, T = 1400: self 3157 vs 3332 us, text context 640 vs 795 us; the two-source
-        // cross-view form is equal, 5888 vs 5882 us: profiles/r03_attn_qt_fold_ab.log); ATTN2_QT = 2 keeps 64-query waves everywhere.
-        // round 4: with the straight-line issue path and four waves per SIMD the 32-query form also wins (by 1-2.5 %) for the two-source launches
-        if (fold && !(two && qt_forced64) && opt(OPT_ATTN2_PF)) return launch_attn2_d<5, 1, true, true>(p, st);      // round 5: permute-free P
-        if (fold) return (two && qt_forced64) ? launch_attn2_d<5, 2, true>(p, st) : launch_attn2_d<5, 1, true>(p, st);
-        return two ? launch_attn2_d<5, 2, false>(p, st) : launch_attn2_d<5, 1, false>(p, st);
-    }
-    return launch_attn2_d<10, 1, false>(p, st);
+    if (r.d != 40) return launch_attn2_d<10, 1, false>(p, tag, st);
+    if (r.pf) return launch_attn2_d<5, 1, true, true>(p, tag, st);
+    if (r.fold) return r.qt == 2 ? launch_attn2_d<5, 2, true>(p, tag, st) : launch_attn2_d<5, 1, true>(p, tag, st);
+    return r.qt == 2 ? launch_attn2_d<5, 2, false>(p, tag, st) : launch_attn2_d<5, 1, false>(p, tag, st);
 }
 
 }  // namespace mdx

@@ -33,6 +33,7 @@
 // measured: no LDS-conflict counter of this kernel is on file, and correctness does not depend on it.
 #include "common.h"
 #include "launch.h"
+#include "attn.h"
 
 namespace mdx {
 
@@ -71,20 +72,15 @@ __global__ __launch_bounds__(CTX_NW * 64) void attn_ctx_rows_kernel(AttnCtxParam
 }
 
 template <int D>
-static int launch_attn_ctx(const AttnCtxParams& p, long blocks, bool pre, bool rows, hipStream_t st) {
+static int launch_attn_ctx(const AttnCtxParams& p, long blocks, bool rows, const char* tag, hipStream_t st) {
     if (rows) hipLaunchKernelGGL((attn_ctx_rows_kernel<D>), dim3((unsigned)blocks), dim3(CTX_NW * 64), 0, st, p);
     else hipLaunchKernelGGL((attn_ctx_kernel<D>), dim3((unsigned)blocks), dim3(CTX_NW * 64), 0, st, p);
-    char tag[64];
-    snprintf(tag, sizeof tag, "attn_ctx_kernel<%d,%s%s>", D, pre ? "pre" : "scaled", rows ? ",rows" : "");
     return check_launch(tag);
 }
 
-}  // namespace mdx
-
-using namespace mdx;
-
-// Host checks + launch of both forms.  rows = false: tk_dev points to one int32; rows = true: to int32 [B], one count per query batch.
-static int attn_ctx_entry(const MdxAttnDesc* a, void* stream, const char* op, bool rows) {
+// Host checks + launch of both forms.  rows = false: a descriptor with tk_dev != NULL, handed on by mdx_attention_* (attention.hip) before
+// every other route; tk_dev points to one int32.  rows = true: mdx_attention_ctx_rows_* below; tk_dev points to int32 [B], one count per query batch.
+int attn_ctx(const MdxAttnDesc* a, hipStream_t st, const char* op, bool rows) {
     if (rows && !a) return set_error(MDX_EINVAL, "%s: null descriptor", op);
     if (rows && !a->tk_dev) return set_error(MDX_EINVAL, "%s: tk_dev is NULL: this entry point takes the device address of int32 [B] key counts", op);
     if (rows && a->kvmap) return set_error(MDX_EINVAL, "%s: tk_dev needs kvmap == NULL (batch b of Q attends to batch b of K / V^T)", op);
@@ -97,14 +93,8 @@ static int attn_ctx_entry(const MdxAttnDesc* a, void* stream, const char* op, bo
     if (!a->q_prescaled && !(a->scale > 0.0)) return set_error(MDX_EINVAL, "%s: tk_dev: scale=%g must be positive (or q_prescaled == 1)", op, a->scale);
     if (!a->Q || !a->K || !a->Vt || !a->O) return set_error(MDX_EINVAL, "%s: null operand", op);
     MDX_NEED(need_aligned(op, "tk_dev", a->tk_dev, 4));
-    MDX_NEED(need_int(op, "B", a->B)); MDX_NEED(need_int(op, "H", a->H)); MDX_NEED(need_int(op, "Tq", a->Tq)); MDX_NEED(need_int(op, "Tk", a->Tk));
     if (a->d % 8 || a->d <= 0) return set_error(MDX_EINVAL, "%s: head dim d=%ld must be a positive multiple of 8", op, (long)a->d);
-    // Q / K rows and V^T rows are read as 16-byte pieces; an O row is written as 8-byte pieces (4 head-dim columns of one query)
-    MDX_NEED(need_multiple(op, "ldq", a->ldq, 8)); MDX_NEED(need_multiple(op, "ldk", a->ldk, 8)); MDX_NEED(need_multiple(op, "ldv", a->ldv, 8));
-    MDX_NEED(need_multiple(op, "sQ", a->sQ, 8)); MDX_NEED(need_multiple(op, "sK", a->sK, 8)); MDX_NEED(need_multiple(op, "sV", a->sV, 8));
-    MDX_NEED(need_multiple(op, "ldo", a->ldo, 4)); MDX_NEED(need_multiple(op, "sO", a->sO, 4));
-    MDX_NEED(need_aligned(op, "Q", a->Q, 16)); MDX_NEED(need_aligned(op, "K", a->K, 16)); MDX_NEED(need_aligned(op, "Vt", a->Vt, 16));
-    MDX_NEED(need_aligned(op, "O", a->O, 8));
+    MDX_NEED(need_attn_layout(op, a));
     if (a->d != 16 && a->d != 32 && a->d != 40 && a->d != 80 && a->d != 160)
         return set_error(MDX_EUNSUPPORTED, "%s: tk_dev: head dim d=%ld has no context-attention kernel instance (d in {16, 32, 40, 80, 160})", op, (long)a->d);
     if (a->Tk > 0 && a->ldv < a->Tk) return set_error(MDX_EINVAL, "%s: tk_dev: ldv=%ld < Tk=%ld (Tk is the capacity)", op, (long)a->ldv, (long)a->Tk);
@@ -113,28 +103,24 @@ static int attn_ctx_entry(const MdxAttnDesc* a, void* stream, const char* op, bo
     const long blocks = a->B * a->H * qblocks;
     MDX_NEED(need_int(op, "B * H * ceil(Tq / 128)", blocks));
     AttnCtxParams p;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.Vt = (const bf16_t*)a->Vt; p.O = (bf16_t*)a->O;
-    p.tk_dev = a->tk_dev;
-    p.H = (int)a->H; p.Tq = (int)a->Tq; p.Tk = (int)a->Tk; p.qblocks = (int)qblocks;
-    p.ldq = a->ldq; p.sQ = a->sQ; p.ldk = a->ldk; p.sK = a->sK; p.ldv = a->ldv; p.sV = a->sV; p.ldo = a->ldo; p.sO = a->sO;
-    p.scale_log2 = a->q_prescaled ? 1.0f : (float)(a->scale * 1.4426950408889634);
-    hipStream_t st = (hipStream_t)stream;
-    const bool pre = a->q_prescaled != 0;
-    switch ((int)a->d) {
-        case 16: return launch_attn_ctx<16>(p, blocks, pre, rows, st);
-        case 32: return launch_attn_ctx<32>(p, blocks, pre, rows, st);
-        case 40: return launch_attn_ctx<40>(p, blocks, pre, rows, st);
-        case 80: return launch_attn_ctx<80>(p, blocks, pre, rows, st);
-        default: return launch_attn_ctx<160>(p, blocks, pre, rows, st);
+    fill_attn_params(p, a);
+    p.tk_dev = a->tk_dev; p.qblocks = (int)qblocks;
+    char tag[64];
+    const AttnRoute r = attn_route_of(a, rows, tag);
+    switch (r.d) {
+        case 16: return launch_attn_ctx<16>(p, blocks, rows, tag, st);
+        case 32: return launch_attn_ctx<32>(p, blocks, rows, tag, st);
+        case 40: return launch_attn_ctx<40>(p, blocks, rows, tag, st);
+        case 80: return launch_attn_ctx<80>(p, blocks, rows, tag, st);
+        default: return launch_attn_ctx<160>(p, blocks, rows, tag, st);
     }
 }
 
-// Entry for descriptors with tk_dev != NULL; called by the public mdx_attention_* (attention_short.hip) before every other route.
-// mdx_attention_ctx_rows_*: public (mdx.h), the same descriptor with tk_dev -> int32 [B]; MDX_OP_ATTN_ROWS in a program.
-#if MDX_F16
-extern "C" int mdx_attention_ctx_f16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_f16", false); }
-extern "C" int mdx_attention_ctx_rows_f16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_ctx_rows_f16", true); }
-#else
-extern "C" int mdx_attention_ctx_bf16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_bf16", false); }
-extern "C" int mdx_attention_ctx_rows_bf16(const MdxAttnDesc* a, void* stream) { return attn_ctx_entry(a, stream, "mdx_attention_ctx_rows_bf16", true); }
-#endif
+}  // namespace mdx
+
+using namespace mdx;
+
+// mdx_attention_ctx_rows_* (_f16 in the fp16 build: launch.h): public (mdx.h), the descriptor of mdx_attention_* with tk_dev -> int32 [B]; MDX_OP_ATTN_ROWS in a program.
+extern "C" int mdx_attention_ctx_rows_bf16(const MdxAttnDesc* a, void* stream) {
+    return attn_ctx(a, (hipStream_t)stream, MDX_F16 ? "mdx_attention_ctx_rows_f16" : "mdx_attention_ctx_rows_bf16", true);
+}

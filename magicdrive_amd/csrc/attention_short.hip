@@ -2,9 +2,7 @@
 //
 // Replaces the attention of transformers' CLIPTextModel (models/clip/modeling_clip.py: CLIPAttention under CLIPTextTransformer's causal mask;
 // the reference pipeline's `text_encoder`, magicdrive/pipeline/pipeline_bev_controlnet.py:148-165): 77 tokens, 12 heads of 64, Q / K / V the
-// three column blocks of one fused [M][3C] projection.  Also the public mdx_attention_* entry point: descriptors with causal == 0 and
-// v_rowmajor == 0 go on, untouched, to the flash kernels' entry in attention.hip (compiled as mdx_attention_long_*, launch.h); a descriptor
-// with tk_dev != NULL (key count read from device memory) goes, before either test, to attention_ctx.hip.
+// three column blocks of one fused [M][3C] projection.  mdx_attention_* (attention.hip) hands descriptors with causal or v_rowmajor set to attn_short below.
 //
 // Shape regime: Tq, Tk <= 128, d in {32, 64}.  Nothing is a multiple of the tile (T = 77), so everything is masked.
 //
@@ -29,30 +27,12 @@
 //   * softmax in fp32 with exp2; P is rounded to the storage type before PV, the row sum is taken of the unrounded values (attention.hip).
 #include "common.h"
 #include "launch.h"
-
-#if MDX_F16
-#define MDX_ATTN_LONG mdx_attention_long_f16
-#else
-#define MDX_ATTN_LONG mdx_attention_long_bf16
-#endif
-// BUILD DEPENDENCY: attention.hip must be compiled with -DMDX_ATTN_LONG_ENTRY (csrc/Makefile sets it for attention.o / attention_f16.o; launch.h
-// then renames its entry point to the symbol declared here).  Without the flag both files define mdx_attention_bf16 / _f16 and the link
-// fails with duplicate symbols; with it on THIS file the public symbol would be missing, hence:
-#ifdef MDX_ATTN_LONG_ENTRY
-#error "attention_short.hip defines the public mdx_attention_* entry points: -DMDX_ATTN_LONG_ENTRY belongs on attention.hip only"
-#endif
-extern "C" int MDX_ATTN_LONG(const MdxAttnDesc* a, void* stream);      // attention.hip
-#if MDX_F16
-#define MDX_ATTN_CTX mdx_attention_ctx_f16
-#else
-#define MDX_ATTN_CTX mdx_attention_ctx_bf16
-#endif
-extern "C" int MDX_ATTN_CTX(const MdxAttnDesc* a, void* stream);       // attention_ctx.hip: key count read from device memory (tk_dev != NULL)
+#include "attn.h"
 
 namespace mdx {
 
 struct AttnShortParams {
-    const bf16_t* Q; const bf16_t* K; const bf16_t* V; bf16_t* O;
+    const bf16_t* Q; const bf16_t* K; const bf16_t* Vt; bf16_t* O;    // Vt: V itself, row-major [Tk][ldv] (the descriptor's field name)
     int H, Tq, Tk;
     long ldq, sQ, ldk, sK, ldv, sV, ldo, sO;
     float scale_log2;  // scale * log2(e)
@@ -86,7 +66,7 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnShortParams p) {
     // ---- stage K and V rows 0 .. roundup32(Tk): clamped loads, rows >= Tk zeroed ----
     {
         const bf16_t* kbase = p.K + (long)b * p.sK + (long)h * D;
-        const bf16_t* vbase = p.V + (long)b * p.sV + (long)h * D;
+        const bf16_t* vbase = p.Vt + (long)b * p.sV + (long)h * D;
         const int rows = (p.Tk + 31) & ~31;
         for (int c = tid; c < rows * CH; c += 256) {
             const int row = c / CH, cc = c - row * CH;
@@ -206,24 +186,15 @@ __global__ __launch_bounds__(256) void attn_short_kernel(AttnShortParams p) {
 }
 
 template <int D16>
-static int launch_attn_short(const AttnShortParams& p, long blocks, bool causal, hipStream_t st) {
+static int launch_attn_short(const AttnShortParams& p, long blocks, bool causal, const char* tag, hipStream_t st) {
     if (causal)
         hipLaunchKernelGGL((attn_short_kernel<D16, true>), dim3((unsigned)blocks), dim3(256), 0, st, p);
     else
         hipLaunchKernelGGL((attn_short_kernel<D16, false>), dim3((unsigned)blocks), dim3(256), 0, st, p);
-    char tag[64];
-    snprintf(tag, sizeof tag, "attn_short_kernel<%d,%s>", D16 * 16, causal ? "causal" : "full");
     return check_launch(tag);
 }
 
-}  // namespace mdx
-
-using namespace mdx;
-
-extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
-    if (a && a->tk_dev) return MDX_ATTN_CTX(a, stream);
-    if (!a || (a->causal == 0 && a->v_rowmajor == 0)) return MDX_ATTN_LONG(a, stream);
-    const char* op = MDX_F16 ? "mdx_attention_f16" : "mdx_attention_bf16";
+int attn_short(const MdxAttnDesc* a, hipStream_t st, const char* op) {
     if (a->causal != 0 && a->causal != 1) return set_error(MDX_EINVAL, "%s: causal=%ld must be 0 or 1", op, (long)a->causal);
     if (a->v_rowmajor != 0 && a->v_rowmajor != 1) return set_error(MDX_EINVAL, "%s: v_rowmajor=%ld must be 0 or 1", op, (long)a->v_rowmajor);
     if (!a->v_rowmajor) return set_error(MDX_EINVAL, "%s: causal needs v_rowmajor == 1 (the short-sequence kernel)", op);
@@ -231,15 +202,9 @@ extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
     if (a->nsrc != 1) return set_error(MDX_EINVAL, "%s: v_rowmajor needs nsrc == 1 (nsrc=%ld)", op, (long)a->nsrc);
     if (a->joint != 0) return set_error(MDX_EINVAL, "%s: v_rowmajor needs joint == 0 (joint=%ld)", op, (long)a->joint);
     if (a->q_prescaled != 0) return set_error(MDX_EINVAL, "%s: v_rowmajor needs q_prescaled == 0 (q_prescaled=%ld)", op, (long)a->q_prescaled);
-    MDX_NEED(need_int(op, "B", a->B)); MDX_NEED(need_int(op, "H", a->H)); MDX_NEED(need_int(op, "Tq", a->Tq)); MDX_NEED(need_int(op, "Tk", a->Tk));
     if (a->causal && a->Tq != a->Tk) return set_error(MDX_EINVAL, "%s: causal needs Tq == Tk (Tq=%ld, Tk=%ld)", op, (long)a->Tq, (long)a->Tk);
     if (a->d % 8 || a->d <= 0) return set_error(MDX_EINVAL, "%s: head dim d=%ld must be a positive multiple of 8", op, (long)a->d);
-    // Q / K / V rows are read as 16-byte pieces; an O row is written as 8-byte pieces (4 head-dim columns of one query)
-    MDX_NEED(need_multiple(op, "ldq", a->ldq, 8)); MDX_NEED(need_multiple(op, "ldk", a->ldk, 8)); MDX_NEED(need_multiple(op, "ldv", a->ldv, 8));
-    MDX_NEED(need_multiple(op, "sQ", a->sQ, 8)); MDX_NEED(need_multiple(op, "sK", a->sK, 8)); MDX_NEED(need_multiple(op, "sV", a->sV, 8));
-    MDX_NEED(need_multiple(op, "ldo", a->ldo, 4)); MDX_NEED(need_multiple(op, "sO", a->sO, 4));
-    MDX_NEED(need_aligned(op, "Q", a->Q, 16)); MDX_NEED(need_aligned(op, "K", a->K, 16)); MDX_NEED(need_aligned(op, "Vt", a->Vt, 16));
-    MDX_NEED(need_aligned(op, "O", a->O, 8));
+    MDX_NEED(need_attn_layout(op, a));
     if (a->d != 32 && a->d != 64)
         return set_error(MDX_EUNSUPPORTED, "%s: v_rowmajor: head dim d=%ld has no short-sequence kernel instance (d in {32, 64})", op, (long)a->d);
     if (a->Tq > SHORT_T || a->Tk > SHORT_T)
@@ -249,10 +214,10 @@ extern "C" int mdx_attention_bf16(const MdxAttnDesc* a, void* stream) {
     const long blocks = a->B * a->H;
     MDX_NEED(need_int(op, "B * H", blocks));
     AttnShortParams p;
-    p.Q = (const bf16_t*)a->Q; p.K = (const bf16_t*)a->K; p.V = (const bf16_t*)a->Vt; p.O = (bf16_t*)a->O;
-    p.H = (int)a->H; p.Tq = (int)a->Tq; p.Tk = (int)a->Tk;
-    p.ldq = a->ldq; p.sQ = a->sQ; p.ldk = a->ldk; p.sK = a->sK; p.ldv = a->ldv; p.sV = a->sV; p.ldo = a->ldo; p.sO = a->sO;
-    p.scale_log2 = (float)(a->scale * 1.4426950408889634);
-    hipStream_t st = (hipStream_t)stream;
-    return a->d == 32 ? launch_attn_short<2>(p, blocks, a->causal != 0, st) : launch_attn_short<4>(p, blocks, a->causal != 0, st);
+    fill_attn_params(p, a);
+    char tag[64];
+    const AttnRoute r = attn_route_of(a, false, tag);
+    return r.d == 32 ? launch_attn_short<2>(p, blocks, a->causal != 0, tag, st) : launch_attn_short<4>(p, blocks, a->causal != 0, tag, st);
 }
+
+}  // namespace mdx

@@ -12,6 +12,7 @@
 #define mdx_conv2d_bf16 mdx_conv2d_f16
 #define mdx_conv2d_direct mdx_conv2d_direct_f16
 #define mdx_attention_bf16 mdx_attention_f16
+#define mdx_attention_ctx_rows_bf16 mdx_attention_ctx_rows_f16
 #define mdx_groupnorm_bf16 mdx_groupnorm_f16
 #define mdx_groupnorm_resident_bf16 mdx_groupnorm_resident_f16
 #define mdx_layernorm_bf16 mdx_layernorm_f16
@@ -26,17 +27,6 @@
 #define mdx_sdpa_bf16 mdx_sdpa_f16
 #define mdx_latent_blend_bf16 mdx_latent_blend_f16
 #define mdx_latent_renoise_bf16 mdx_latent_renoise_f16
-#endif
-// mdx_attention_* itself is defined in attention_short.hip (ABI 12): it checks the causal / v_rowmajor fields, serves the short-sequence
-// kernel and passes every other descriptor on to the flash kernels' entry point.  That one stays where it was, in attention.hip, which
-// csrc/Makefile compiles with -DMDX_ATTN_LONG_ENTRY so that it is emitted under the internal name mdx_attention_long_*.
-#ifdef MDX_ATTN_LONG_ENTRY
-#undef mdx_attention_bf16
-#if defined(MDX_F16) && MDX_F16
-#define mdx_attention_bf16 mdx_attention_long_f16
-#else
-#define mdx_attention_bf16 mdx_attention_long_bf16
-#endif
 #endif
 
 // process-wide runtime state (api.hip): ONE instance shared by the bf16 and the fp16 build of the kernels

@@ -60,15 +60,15 @@ CONSTANTS = {          # key: (value, "file:line[-line]", text that must stand o
     "gemm_xl.XL_SLOTS": (12, "gemm_route.h:26", "XL_SLOTS = 12"),
     "gemm_xl.raster_mt": (64, "gemm_xl.hip:1070-1081", "q.mt >= 64"),
     "attn.KVT": (64, "attention.hip:44", "KVT = 64"),
-    "attn.NW": ((1, 2, 4, 8), "attention.hip:365-368", "launch_attn<D16, 1>(p, st)"),
+    "attn.NW": ((1, 2, 4, 8), "attention.hip:353", "launch_attn<D16, 1>(p, tag, st)"),
     "attn.wave_q": (32, "attention.hip:333", "NW * 32"),
     "attn2.A2_KV": (64, "attention2.hip:40", "A2_KV = 64"),
     "attn2.sub": (32, "attention2.hip:523", "A2_KV <= 32"),
-    "attn2.min_Tq": (256, "attention2.hip:805", "p.Tq < 256"),
-    "attn2.q64_Tq": (512, "attention2.hip:816", "p.Tq >= 512"),
+    "attn2.min_Tq": (256, "attn_route.h:43", "p.Tq < 256"),
+    "attn2.q64_Tq": (512, "attn_route.h:72", "p.Tq >= 512"),
     "attn2.res_tiles": (3, "attention2.hip:38", "#define A2_RING 3"),
-    "attn_short.SHORT_T": (128, "attention_short.hip:61", "SHORT_T = 128"),
-    "attn_short.sub": (32, "attention_short.hip:61", "4 sub-tiles of 32 kv"),
+    "attn_short.SHORT_T": (128, "attention_short.hip:41", "SHORT_T = 128"),
+    "attn_short.sub": (32, "attention_short.hip:41", "4 sub-tiles of 32 kv"),
     "gn.vec": ((8, 4, 2, 1), "norm.hip:519-522", "for (int v = 8; v > 1; v >>= 1)"),
     "gn.threads": (1024, "norm.hip:21", "GN_THREADS = 1024"),
     "gn2.U": (4, "norm.hip:184", "GN2_U = 4"),

@@ -328,6 +328,10 @@ TABLE += [
     (L.OP_UNIPC, "xin_ld is not negative", unipc(x_in=P(8), xin_ld=-8, xin_c=4), EINVAL, "xin_ld=-8"),
     (L.OP_UNIPC, "x_in at its element's alignment (4 / 2 bytes)", unipc(x_in=P(8) + 1, xin_ld=8, xin_c=4), EINVAL, "x_in must be 2-byte"),
     (L.OP_UNIPC, "x_in at its element's alignment (4 / 2 bytes)", unipc(x_in=P(8) + 2), EINVAL, "x_in must be 4-byte"),
+    # the checks of the context (tk_dev) and the short-sequence (v_rowmajor) route of mdx_attention_* (tests/test_attn_contract.py has their whole tables)
+    (L.OP_ATTN, "tk_dev 4-byte aligned", attn(tk_dev=P(6) + 2, d=16), EINVAL, "tk_dev must be 4-byte"),
+    (L.OP_ATTN, "tk_dev: B * H * ceil(Tq / 128) fits a 32-bit int", attn(tk_dev=P(6), d=16, B=1 << 16, H=1 << 16), EINVAL, "B * H * ceil(Tq / 128)=4294967296"),
+    (L.OP_ATTN, "v_rowmajor: B * H fits a 32-bit int", attn(v_rowmajor=1, d=32, B=1 << 16, H=1 << 16, ldv=1 << 21), EINVAL, "B * H=4294967296"),
 ]
 
 
@@ -383,6 +387,32 @@ def with_latent_helpers(body):
     return body + "".join("\n" + hb for name, hb in latent_helper_bodies().items() if name + "(" in body)
 
 
+def attn_helper_bodies():
+    """{name: body} of what mdx_attention_* calls for its checks: the layout checks every attention route shares (csrc/attn.h:
+    need_attn_layout) and the routes that run their own checks (attn_short, attn_ctx)."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "magicdrive_amd", "csrc")
+    src = lambda f: open(os.path.join(csrc, f)).read()
+    bodies = dict(re.findall(r"inline int (need_attn_layout)\(const char\* op, const MdxAttnDesc\* a\) \{\n(.*?)\n\}", src("attn.h"), re.S))
+    for f in ("attention_short.hip", "attention_ctx.hip"):
+        bodies.update(re.findall(r"\nint (attn_\w+)\(const MdxAttnDesc\* a, hipStream_t st, const char\* op[^)]*\) \{\n(.*?)\n\}", src(f), re.S))
+    assert set(bodies) == {"need_attn_layout", "attn_short", "attn_ctx"}, sorted(bodies)
+    return bodies
+
+
+def with_attn_helpers(body):
+    """An entry point's body plus the body of everything of attn_helper_bodies that it calls, followed to the end (a route calls the
+    shared layout checks itself)."""
+    helpers, seen = attn_helper_bodies(), set()
+    while True:
+        more = [n for n in helpers if n not in seen and n + "(" in body]
+        if not more:
+            return body
+        seen |= set(more)
+        body += "".join("\n" + helpers[n] for n in more)
+
+
 def _host_checks():
     """(entry point, field) of every need_int / need_multiple / need_aligned call with a literal field name in the entry points' sources."""
     import os
@@ -393,12 +423,13 @@ def _host_checks():
         parts = re.split(r'extern "C" int (mdx_\w+)\(', open(os.path.join(csrc, fn)).read())
         shared = re.findall(r'need_\w+\(op, "([^"]+)"', parts[0])          # helpers ahead of the first entry point (check_epilogue_operands)
         for name, body in zip(parts[1::2], parts[2::2]):
-            body = with_latent_helpers(body.split("\nnamespace mdx {")[0])
+            body = with_attn_helpers(with_latent_helpers(body.split("\nnamespace mdx {")[0]))
             fields = re.findall(r'need_\w+\((?:op|"mdx_\w+"), "([^"]+)"', body)
             if "check_epilogue_operands(" in body:
                 fields += shared
             found |= {(name, f) for f in fields}
     assert {(e, f) for e in ("mdx_cfg_ddim_step", "mdx_cfg_unipc_step") for f in ("x_in", "xin_c", "xin_ld")} <= found
+    assert {("mdx_attention_bf16", f) for f in ("ldq", "Vt", "tk_dev", "B * H", "B * H * ceil(Tq / 128)")} <= found
     return found
 
 

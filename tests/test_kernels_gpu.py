@@ -1198,3 +1198,35 @@ def test_attention2_crossview(dev, b, heads, T, d, pre):
             j = (i // ncam) * ncam + pair[i % ncam][s]
             ref[i] += ref_attention(qc[i:i + 1], kc[j:j + 1], vc[j:j + 1], heads, d ** -0.5)[0]
     close(o, ref, name=f"attn2 cross-view{' prescaled' if pre else ''}")
+
+
+# ---- one smallest shape per attention family: the kernel the library reports is the one csrc/attn_route.h names -------------------
+ROUTE_FAMILIES = {
+    "flash": dict(name="flash", B=1, H=1, Tq=33, d=16, pre=False, kmult=1),
+    "attn2": dict(name="attn2", B=8, H=8, Tq=256, d=40, pre=False, kmult=1),
+    "resident": dict(name="resident", B=8, H=8, Tq=256, Tk=192, d=40, pre=True, kmult=1, opts={"ATTN2_RES": 2}),
+    "short": dict(name="short", B=2, H=2, Tq=5, d=32, pre=False, kmult=3, causal=True, rowmajor=True),
+    "ctx": dict(name="ctx", B=2, H=2, Tq=33, Tk=40, d=16, pre=False, kmult=1, ctx="dev", live=27),
+}
+
+
+@pytest.fixture(scope="module")
+def family_routes(tmp_path_factory):
+    """What tests/attn_route_check.cpp (g++, the header alone) says for the five descriptors."""
+    import attn_route_table as T
+    cases = {k: dict(T.DEFAULTS, **c) for k, c in ROUTE_FAMILIES.items()}
+    out = T.evaluate([f"{k} {T.route_line(c)}" for k, c in cases.items()], tmp_path_factory.mktemp("attn_route"))
+    if out is None:
+        pytest.skip("no g++")
+    return out
+
+
+@pytest.mark.parametrize("f16", [False, True], ids=["bf16", "f16"])
+@pytest.mark.parametrize("family", list(ROUTE_FAMILIES))
+def test_attention_family_runs_the_kernel_the_route_header_names(dev, family_routes, family, f16):
+    import attn_route_table as T
+    tag, o, ref = T.run_case(dict(T.DEFAULTS, **ROUTE_FAMILIES[family], f16=f16), values=True)
+    want = family_routes[family]
+    assert tag == want["tag"], (tag, want)
+    assert want["family"] == {"resident": "attn2-resident"}.get(family, family), want
+    close(o, ref, name=f"attn family {family}", kind="f16" if f16 else "bf16")

@@ -52,7 +52,7 @@ def test_edges_and_constants():
     assert "constexpr int A2_KV = 64, A2_NW = 4, A2_NT = 256, A2_NBUF = A2_RING;" in src("attention2.hip") and "#define A2_RING 3" in src("attention2.hip")
     assert "constexpr int SHORT_T = 128;" in src("attention_short.hip")
     assert "constexpr int XL_SLOTS = 12;" in src("gemm_route.h")
-    assert "if (p.Tq < 256 || (long)((p.Tq + 127) / 128) * p.H * p.B < 128) return false;" in src("attention2.hip")
+    assert "if (p.Tq < 256 || (long)((p.Tq + 127) / 128) * p.H * p.B < 128) return false;" in src("attn_route.h")
 
 
 # --------------------------------------------------------------------------------------------------------------------------------------

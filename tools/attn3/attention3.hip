@@ -38,7 +38,7 @@
 #include "options.h"
 #include "xl_layout.h"
 #include "xl_dma.h"
-#include "attn2.h"
+#include "attn.h"
 #include "attn3_layout.h"
 
 namespace mdx {

@@ -24,8 +24,6 @@ def ksrcs(tree):
 
 def compile_s(tree, src, f16, out):
     extra = ["-DMDX_F16=1", "-Dmdx=mdx_f16"] if f16 else []
-    if src == "attention.hip":
-        extra.append("-DMDX_ATTN_LONG_ENTRY")
     r = subprocess.run([HIPCC] + FLAGS + extra + ["--cuda-device-only", "-S", os.path.join(tree, "magicdrive_amd", "csrc", src), "-o", out], capture_output=True, text=True)
     if r.returncode:                 # keep the compiler's diagnostic (its warnings on success are dropped)
         sys.stderr.write(r.stderr)
