@@ -602,6 +602,49 @@ typedef struct MdxRenoiseDesc {
 } MdxRenoiseDesc;
 int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream);
 
+/*
+ * mdx_image_composite_bf16 / _f16 — composite a kept-region edit with the recorded pictures: every pixel outside the edited regions
+ * becomes the recorded pixel again, bit for bit, and a feathered band inside the kept region hides the seam (additive symbols, the ABI
+ * version stays 12; MDX_OP_IMAGE_COMPOSITE; csrc/composite.hip; mdx_last_kernel() starts with "composite_kernel").  An op on the VAE
+ * decoder's output, outside the sampler's plan.  The two builds differ only in the 16-bit type of gen (gen_f32 == 0).
+ *   gen   : [V][C][H][W] decoder output in [-1, 1], planar: element (v, c, y, x) at gen + v * g_sv + c * g_sc + y * g_ld + x (strides in
+ *           elements); the build's 16-bit type, or fp32 when gen_f32 == 1;
+ *   orig  : fp32 [V][H][W][C] recorded pictures in [0, 1], contiguous;
+ *   keep  : fp32 [V][H / f][W / f] keep masks at latent resolution, contiguous: 1 keeps, 0 regenerates.  The values are device data and
+ *           taken as they are; callers validate them (the pipeline does, on the host);
+ *   out   : fp32 [V][H][W][C], contiguous: the composited pictures, the layout decode_latents hands to numpy;
+ *   matte : NULL, or fp32 [V][H][W], contiguous: receives w;
+ *   has   : NULL (every view has a picture), or uint8 [V]: has[v] == 0 is a view without a picture — out = g, matte = 0, and the orig and
+ *           keep rows of that view are NOT read.
+ * The matte of a view, with r = feather image pixels and every coordinate clamped to the image (edge replicate):
+ *   a(y, x) = keep[y / f][x / f];
+ *   e(y, x) = min of a over the (2r+1)^2 window around (y, x)                                   (erosion);
+ *   w(y, x) = S / (2r+1)^2, S the fp32 sum of e over the (2r+1)^2 window around (y, x)          (one IEEE division).
+ * S is summed along the row first, then down the column, each sequentially.  For masks on the 1/64 grid every sum is exact, whatever the
+ * order.  r == 0: w = a.  w = 0 wherever a = 0, w = 1 wherever every a within Chebyshev distance 2r is 1, and the transition band of
+ * width 2r lies inside the kept region.  Next to the image border w = 0 may reach a few pixels past a = 0 (the clamped window is cut).
+ * The blend, per pixel and channel, with round16 = rounding to gen's 16-bit type (not applied when gen_f32):
+ *   g = clamp01(float(round16(fmaf(gen, 0.5, 0.5))))      the bits of (image / 2 + 0.5).clamp(0, 1).float(): NaN stays NaN, +Inf -> 1, -Inf -> 0;
+ *   w == 0 : out = g;   w == 1 : out = orig (a non-finite gen does not reach a fully kept pixel);   else : out = fmaf(w, orig - g, g).
+ * One launch, one workgroup per (view, 32 x 64 pixel tile); the tile's patch of keep cells with its halo of 2r pixels is staged in LDS
+ * once and both separable passes run out of LDS.  fp32 math, no atomics, 64-bit addressing, deterministic: a view's bits depend on that
+ * view's operands only — not on V, not on the tile walk, not on whether matte is given.  16-byte accesses of gen when gen and the byte
+ * sizes of g_ld, g_sc, g_sv are multiples of 16, of orig / out when both are 16-byte aligned and W * C % 4 == 0, of matte when it is
+ * 16-byte aligned and W % 4 == 0; any other case is SERVED by scalar accesses with the same bits.  Nothing is read or written outside
+ * the described extents: W elements of each gen row, V * H * W * C floats of orig / out, V * (H / f) * (W / f) of keep, V * H * W of matte,
+ * V bytes of has.
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): gen, orig, keep, out not NULL (matte and
+ * has may be NULL); gen at its element's alignment (2 / 4 bytes); orig, keep, out, matte 4-byte aligned; V not negative; C in [1, 4];
+ * H, W >= 1; f >= 1 and divides H and W; feather in [0, 16]; gen_f32 in {0, 1}; g_ld >= W; g_sc, g_sv not negative; V, C, H, W, f,
+ * feather and H * W fit a 32-bit int.  V == 0: MDX_OK (after the checks), nothing is launched.
+ */
+typedef struct MdxCompositeDesc {
+    const void* gen; const float* orig; const float* keep; float* out; float* matte; const uint8_t* has;
+    int64_t V, C, H, W, f, feather, gen_f32;
+    int64_t g_sv, g_sc, g_ld;
+} MdxCompositeDesc;
+int mdx_image_composite_bf16(const MdxCompositeDesc* d, void* stream);
+
 /* ---- program = array of ops, executed in order on one stream ------------ */
 #define MDX_OP_GEMM 1
 #define MDX_OP_CONV 2
@@ -622,6 +665,7 @@ int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream);
 #define MDX_OP_SDPA 17                 /* MdxSdpaDesc through mdx_sdpa_* */
 #define MDX_OP_LATENT_BLEND 18         /* MdxBlendDesc through mdx_latent_blend_* */
 #define MDX_OP_LATENT_RENOISE 19       /* MdxRenoiseDesc through mdx_latent_renoise_* */
+#define MDX_OP_IMAGE_COMPOSITE 20      /* MdxCompositeDesc through mdx_image_composite_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -657,6 +701,7 @@ int mdx_group_stats_f16(const MdxStatsDesc* d, void* stream);
 int mdx_sdpa_f16(const MdxSdpaDesc* d, void* stream);
 int mdx_latent_blend_f16(const MdxBlendDesc* d, void* stream);
 int mdx_latent_renoise_f16(const MdxRenoiseDesc* d, void* stream);
+int mdx_image_composite_f16(const MdxCompositeDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -152,3 +152,43 @@ def box_keep_mask(corners_2d, kept, image_hw, latent_hw, dilate: int = 1) -> tor
     if dilate > 0:
         cover = torch.nn.functional.max_pool2d(cover.unsqueeze(1), 2 * int(dilate) + 1, stride=1, padding=int(dilate)).squeeze(1)
     return (1.0 - cover).clamp_(0.0, 1.0)
+
+
+def edit_matte(keep, factor: int, feather: int) -> torch.Tensor:
+    """The matte of a kept-region composite, (..., h, w) keep masks in [0, 1] -> (..., h * factor, w * factor) fp32 weights of the
+    RECORDED picture: the definition the library's op computes on the device (ops.ImageComposite, include/mdx.h: MdxCompositeDesc), in
+    plain torch on the tensor's own device.  The product path never calls this: it is the documented meaning of the op and what
+    CPU-only callers use.
+
+        a = keep repeated `factor` times along both axes (nearest upsample);
+        e = min of a over the (2 feather + 1)^2 window, the image padded by edge replication (erosion);
+        w = mean of e over the same window, padded likewise.
+
+    feather is in IMAGE pixels, 0 to 16; 0 returns a.  w = 0 wherever a = 0 (generated content is never attenuated inside the
+    regenerated region), w = 1 wherever every a within Chebyshev distance 2 feather is 1, and the transition band of width 2 feather lies
+    inside the kept region, where both sources show the same picture up to the VAE's error.  Next to the image border w = 0 may reach a
+    few pixels past a = 0: the clamped window is cut by the border."""
+    import torch.nn.functional as F
+    k = torch.as_tensor(keep)
+    if not k.dtype.is_floating_point:
+        k = k.float()
+    if k.dim() < 2:
+        raise ValueError(f"edit_matte: keep must be (..., h, w), got {tuple(k.shape)}")
+    if not (isinstance(factor, int) and not isinstance(factor, bool) and factor >= 1):
+        raise ValueError(f"edit_matte: factor={factor!r} must be an integer >= 1")
+    if not (isinstance(feather, int) and not isinstance(feather, bool) and 0 <= feather <= 16):
+        raise ValueError(f"edit_matte: feather={feather!r} must be an integer in [0, 16]")
+    a = k.repeat_interleave(factor, dim=-2).repeat_interleave(factor, dim=-1)
+    if feather == 0:
+        return a.float() if a.dtype != torch.float64 else a
+    r, n = feather, 2 * feather + 1
+    x = a.reshape(-1, 1, *a.shape[-2:])
+
+    def pad(t):                     # edge replication of any width (F.pad's replicate mode needs the pad to be smaller than the image)
+        iy = torch.arange(-r, t.shape[-2] + r, device=t.device).clamp_(0, t.shape[-2] - 1)
+        ix = torch.arange(-r, t.shape[-1] + r, device=t.device).clamp_(0, t.shape[-1] - 1)
+        return t[..., iy, :][..., ix]
+
+    e = -F.max_pool2d(-pad(x), n, stride=1)
+    w = F.avg_pool2d(pad(e), n, stride=1)
+    return w.reshape(a.shape)

@@ -82,6 +82,9 @@ def op_bytes(op) -> float:
     if isinstance(op, O.LatentRenoise):
         # 0 MFMA flops; x read and written, the seeds, the x_in copies (the noise is never in memory)
         return 2 * nb(op.x) + nb(op.seeds) + nb(op.x_in)
+    if isinstance(op, O.ImageComposite):
+        # 0 MFMA flops; gen and orig read, out (and the matte) written, the keep cells and the has bytes
+        return nb(op.gen) + nb(op.orig) + nb(op.keep) + nb(op.out) + nb(op.matte) + nb(op.has)
     if isinstance(op, (O.Ew, O.Upsample, O.Layout)):
         return nb(op.X) + nb(op.Y) * (2 if getattr(op, "kind", 0) == 1 else 1)
     return 0.0

@@ -805,6 +805,50 @@ class LatentRenoise:
         return self.opcode, d
 
 
+@dataclass
+class ImageComposite:
+    """Composite a kept-region edit with the recorded pictures (MdxCompositeDesc, csrc/composite.hip), on the VAE decoder's output.
+    gen [V, C, H, W] in [-1, 1]: bf16, fp16 or fp32, a view with unit inner stride (a channel slice or a wider row pitch is taken as it
+    is); orig fp32 [V, H, W, C] in [0, 1]; keep fp32 [V, H / f, W / f]; out fp32 [V, H, W, C]; matte None or fp32 [V, H, W]; has None or
+    uint8 [V] (0: no picture for this view — out is the plain picture, the matte 0).  With w the matte of magicdrive_amd.dataset.edit_matte
+    (keep, f, feather) and g = (gen / 2 + 0.5).clamp(0, 1).float(): out = g where w == 0, orig where w == 1, fma(w, orig - g, g) between."""
+    gen: torch.Tensor
+    orig: torch.Tensor
+    keep: torch.Tensor
+    out: torch.Tensor
+    feather: int
+    matte: Optional[torch.Tensor] = None
+    has: Optional[torch.Tensor] = None
+    name: str = ""
+    opcode = L.OP_IMAGE_COMPOSITE
+
+    def lower(self):
+        gen, orig, keep, out = self.gen, self.orig, self.keep, self.out
+        what = f"composite {self.name}"
+        _chk(gen.dim() == 4 and gen.dtype in (F32,) + H16, f"{what}: gen must be [V, C, H, W], fp32 or 16-bit, got {tuple(gen.shape)} {gen.dtype}")
+        V, Cc, H, W = gen.shape
+        _chk(1 <= Cc <= 4 and H >= 1 and W >= 1, f"{what}: gen {tuple(gen.shape)}: 1 to 4 channels, H, W >= 1")
+        _chk((W == 1 or gen.stride(3) == 1) and (H == 1 or gen.stride(2) >= W) and all(s >= 0 for s in gen.stride()), f"{what}: gen needs a unit inner stride and a row stride >= W, got {gen.stride()}")
+        _chk(orig.dtype == F32 and tuple(orig.shape) == (V, H, W, Cc) and orig.is_contiguous(), f"{what}: orig must be fp32 [V, H, W, C] = {(V, H, W, Cc)}, dense")
+        _chk(out.dtype == F32 and tuple(out.shape) == (V, H, W, Cc) and out.is_contiguous(), f"{what}: out must be fp32 [V, H, W, C] = {(V, H, W, Cc)}, dense")
+        _chk(keep.dtype == F32 and keep.dim() == 3 and keep.shape[0] == V and keep.is_contiguous() and keep.shape[1] >= 1 and keep.shape[2] >= 1,
+             f"{what}: keep must be fp32 [V, h, w], dense")
+        f = H // keep.shape[1]
+        _chk(f >= 1 and keep.shape[1] * f == H and keep.shape[2] * f == W, f"{what}: keep {tuple(keep.shape[1:])} is not the image {(H, W)} divided by one whole factor")
+        _chk(isinstance(self.feather, int) and not isinstance(self.feather, bool) and 0 <= self.feather <= 16, f"{what}: feather={self.feather!r} must be an integer in [0, 16]")
+        if self.matte is not None:
+            _chk(self.matte.dtype == F32 and tuple(self.matte.shape) == (V, H, W) and self.matte.is_contiguous(), f"{what}: matte must be fp32 [V, H, W], dense")
+        if self.has is not None:
+            _chk(self.has.dtype == torch.uint8 and tuple(self.has.shape) == (V,) and self.has.is_contiguous(), f"{what}: has must be uint8 [V]")
+        others = [t for t in (orig, keep, out, self.matte, self.has) if t is not None]
+        _chk(all(t.device == gen.device for t in others), f"{what}: every operand must be on the device of gen")
+        d = L.MdxCompositeDesc()
+        d.gen, d.orig, d.keep, d.out, d.matte, d.has = _p(gen), _p(orig), _p(keep), _p(out), _p(self.matte), _p(self.has)
+        d.V, d.C, d.H, d.W, d.f, d.feather, d.gen_f32 = V, Cc, H, W, f, self.feather, int(gen.dtype == F32)
+        d.g_sv, d.g_sc, d.g_ld = (gen.stride(0) if V > 1 else Cc * H * gen.stride(2)), (gen.stride(1) if Cc > 1 else 0), (gen.stride(2) if H > 1 else W)
+        return self.opcode, d
+
+
 def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, scale: Optional[float] = None, causal: bool = False,
          key_lengths: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """softmax(scale * q k^T + mask) v per head on the GPU kernel behind mdx_sdpa_* (ops.Sdpa), on torch's current stream.
@@ -824,6 +868,22 @@ def sdpa(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, *, scale
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     run_ops([Sdpa(q, k, v, out, heads=heads, scale=scale, causal=causal, klen=key_lengths)])
     return out
+
+
+def image_composite(gen: torch.Tensor, orig: torch.Tensor, keep: torch.Tensor, feather: int, *, has: Optional[torch.Tensor] = None,
+                    return_matte: bool = False):
+    """Composite decoded views with their recorded pictures on the GPU kernel behind mdx_image_composite_* (ops.ImageComposite), on
+    torch's current stream.  gen [V, C, H, W] (bf16, fp16 or fp32, in [-1, 1]), orig fp32 [V, H, W, C] in [0, 1], keep fp32
+    [V, H / f, W / f], feather in image pixels (0 to 16), has uint8 [V] or None.  Returns out fp32 [V, H, W, C], or (out, matte [V, H, W])."""
+    for t in (gen, orig, keep):
+        if not t.is_cuda:
+            raise RuntimeError("magicdrive_amd: ops.image_composite runs on the MI355X only (no CPU fallback; dataset.edit_matte states the matte in torch)")
+    _chk(gen.dim() == 4, f"image_composite: gen must be [V, C, H, W], got {tuple(gen.shape)}")
+    V, Cc, H, W = gen.shape
+    out = torch.empty(V, H, W, Cc, dtype=F32, device=gen.device)
+    matte = torch.empty(V, H, W, dtype=F32, device=gen.device) if return_matte else None
+    run_ops([ImageComposite(gen, orig, keep, out, feather, matte=matte, has=has)])
+    return (out, matte) if return_matte else out
 
 
 def dtype_code(op) -> int:

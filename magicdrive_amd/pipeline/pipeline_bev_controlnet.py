@@ -59,6 +59,7 @@ class BEVStableDiffusionPipelineOutput:
     images: Union[List[List[Any]], np.ndarray, torch.Tensor]
     nsfw_content_detected: Optional[List[bool]]
     health: Optional[SampleHealth] = None           # pipe.health is None: None
+    matte: Optional[np.ndarray] = None              # pipe.composite_images is None: None; else [B, n_cam, H, W], the weight of the recorded picture
 
 
 class _NullBar:
@@ -128,9 +129,22 @@ class StableDiffusionBEVControlNetPipeline:
         # mixes (a box edge inside the 8x8 image pixels of a latent pixel).  None on a view WITH a conditional latent keeps the whole view;
         # a view without one is regenerated and takes no mask.  After every step but the last the sample becomes
         # m * add_noise(cond, noise, t_next) + (1 - m) * sample (ops.LatentBlend behind the scheduler op): the kept background of the
-        # result is the model's own last-step output given that context, NOT the encoded input; a pixel-space composite with the
-        # original pictures is left to the caller.  magicdrive_amd.dataset.regions.box_keep_mask builds the masks from projected boxes.
+        # result is the model's own last-step output given that context, NOT the encoded input; pipe.composite_images (below) puts the
+        # recorded pixels back outside the edited regions.  magicdrive_amd.dataset.regions.box_keep_mask builds the masks from projected boxes.
         self.keep_masks: Optional[List[List[Optional[torch.Tensor]]]] = None
+        # Composite a kept-region edit with the RECORDED pictures, on the device (with keep_masks only; attributes like keep_masks).
+        # None (default): today's path, decode_latents byte for byte what it is.  Set: a B x N_cam list, each entry None or an (H, W, 3)
+        # picture — a uint8 array / tensor is taken as k / 255, a floating one must be finite and in [0, 1].  Behind the VAE decoder (and
+        # behind the health image records, which still see the raw decoded tensor) ONE ops.ImageComposite launch on the decode's stream
+        # turns each view into w * recorded + (1 - w) * generated, w = dataset.edit_matte(keep mask, 8, composite_feather): the keep mask
+        # upsampled to the image, eroded by composite_feather image pixels and box-filtered by the same radius.  w == 1 returns the
+        # recorded pixel bit for bit (numpy_to_pil_double then gives back the recorded byte), w == 0 the bits of the plain path; the
+        # transition band of width 2 * composite_feather lies INSIDE the kept region, and next to the image border w = 0 may reach a few
+        # pixels past the regenerated region.  A None entry leaves its view as the plain path gives it.  output.matte holds w.
+        # output_type="latent", a picture on a view without a conditional latent, a wrong shape or range: ValueError before any device work.
+        # Nobody has looked at composited pictures from trained weights: the feature is the mechanism and its exactness guarantees.
+        self.composite_images: Optional[List[List[Any]]] = None
+        self.composite_feather: int = 4
         # RePaint resampling of a kept-region edit (Lugmayr et al. 2022; with keep_masks only, DDIM only; an attribute like keep_masks).
         # None (default): today's path, plan key included.  (jump_length, jump_n_sample), integers >= 1: the loop follows
         # schedulers.resample_actions(num_steps, jump_length, jump_n_sample) — after the step at every jump_length-th index the sample is
@@ -267,10 +281,13 @@ class StableDiffusionBEVControlNetPipeline:
             raise RuntimeError("If you fixed the logic for generator, please remove this. Otherwise, please use other sampler.")
         return {"eta": eta} if "eta" in params else {}
 
-    def decode_latents(self, latents, _records=None):
+    def decode_latents(self, latents, _records=None, _composite=None):
         """pipeline_bev_controlnet.py:100-112 (5-D latents); VAE is a caller-supplied torch module.
         _records: a list that receives the device-side health records [views, 4] of the decoded tensor (before the clamp, which would
-        turn +-Inf into valid pixels); not part of the reference signature."""
+        turn +-Inf into valid pixels); not part of the reference signature.
+        _composite: (orig fp32 [views, H, W, 3], has uint8 [views], keep fp32 [views, h, w], feather, sink) from _checked_composite, host
+        tensors: the decoded tensor goes through ops.ImageComposite instead of the clamp / permute / float below, and sink (a list)
+        receives the matte [B, n_cam, H, W], still on the device; likewise not part of the reference signature."""
         if self.vae is None:
             raise ValueError("no VAE attached: use output_type='latent' or pass vae= to the pipeline")
         sf = getattr(getattr(self.vae, "config", None), "scaling_factor", 0.18215)
@@ -280,6 +297,20 @@ class StableDiffusionBEVControlNetPipeline:
         image = self.vae.decode(x.to(vdt)).sample
         if _records is not None:
             _records.append(self._image_records(image))
+        if _composite is not None:
+            from .. import ops as O
+            orig, has, keep, feather, sink = _composite
+            if image.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                raise TypeError(f"composite of a {image.dtype} image: the kernel reads fp32, bf16 or fp16")
+            if not image.is_cuda:
+                raise RuntimeError("the composite is computed on the MI355X only: the decoded image is not a device tensor")
+            if image.stride(-1) != 1 or image.stride(-2) < image.shape[-1]:
+                image = image.contiguous()
+            dev = image.device
+            with torch.cuda.device(dev):
+                out, matte = O.image_composite(image, orig.to(dev), keep.to(dev), feather, has=has.to(dev), return_matte=True)
+            sink.append(matte.reshape(bs, -1, *matte.shape[1:]))
+            return out.reshape(bs, -1, *out.shape[1:]).cpu().numpy()
         image = image.reshape(bs, -1, *image.shape[1:])
         image = (image / 2 + 0.5).clamp(0, 1)
         return image.cpu().permute(0, 1, 3, 4, 2).float().numpy()
@@ -404,6 +435,46 @@ class StableDiffusionBEVControlNetPipeline:
                 out[i, j] = mf
         return out
 
+    def _checked_composite(self, given_view, height: int, width: int, output_type) -> Tuple[torch.Tensor, torch.Tensor, int]:
+        """pipe.composite_images as (orig fp32 [B * N_cam, H, W, 3] in [0, 1], has uint8 [B * N_cam], feather), host tensors; a None entry
+        -> has 0 and a zero picture the kernel never reads.  Every refusal is a ValueError raised here, before any device work of the call."""
+        pics, r = self.composite_images, self.composite_feather
+        if getattr(self, "keep_masks", None) is None:
+            raise ValueError("composite_images is set without keep_masks: the composite puts the recorded pictures back where the latents were "
+                             "KEPT (set pipe.keep_masks, or pipe.composite_images = None)")
+        if output_type == "latent":
+            raise ValueError("composite_images with output_type='latent': the composite is an op on decoded pictures (ask for 'pil' or 'np', or "
+                             "set pipe.composite_images = None)")
+        if not (isinstance(r, (int, np.integer)) and not isinstance(r, bool) and 0 <= r <= 16):
+            raise ValueError(f"composite_feather={r!r}: an integer number of image pixels in [0, 16]")
+        cond_lat = given_view[0]                               # keep_masks passed its checks: given views exist
+        if not isinstance(pics, (list, tuple)) or len(pics) != len(cond_lat) or any(not isinstance(pr, (list, tuple)) or len(pr) != len(cr) for pr, cr in zip(pics, cond_lat)):
+            got = [len(pr) if isinstance(pr, (list, tuple)) else "?" for pr in pics] if isinstance(pics, (list, tuple)) else type(pics).__name__
+            raise ValueError(f"composite_images must be a B x N_cam list like conditional_latents: got {got} rows for {[len(cr) for cr in cond_lat]}")
+        n_cam = max((len(cr) for cr in cond_lat), default=0)
+        orig = torch.zeros(len(cond_lat) * n_cam, height, width, 3, dtype=torch.float32)
+        has = torch.zeros(len(cond_lat) * n_cam, dtype=torch.uint8)
+        for i, (pr, cr) in enumerate(zip(pics, cond_lat)):
+            for j, (pic, v) in enumerate(zip(pr, cr)):
+                if pic is None:
+                    continue
+                if v is None:
+                    raise ValueError(f"composite_images[{i}][{j}]: a picture on a view without a conditional latent (nothing is kept there)")
+                t = pic.detach().cpu() if isinstance(pic, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(pic)))
+                if tuple(t.shape) != (height, width, 3):
+                    raise ValueError(f"composite_images[{i}][{j}]: shape {tuple(t.shape)}, expected the picture size ({height}, {width}, 3)")
+                if t.dtype == torch.uint8:
+                    o = t.to(torch.float32) / 255.0
+                elif t.dtype.is_floating_point:
+                    o = t.to(torch.float32)
+                    if not bool(torch.isfinite(o).all()) or float(o.min()) < 0.0 or float(o.max()) > 1.0:
+                        raise ValueError(f"composite_images[{i}][{j}]: floating values must be finite and in [0, 1]")
+                else:
+                    raise ValueError(f"composite_images[{i}][{j}]: dtype {t.dtype}: uint8 (taken as k / 255) or floating in [0, 1]")
+                orig[i * n_cam + j] = o
+                has[i * n_cam + j] = 1
+        return orig, has, int(r)
+
     def _plan_config(self) -> Dict[str, Any]:
         """Architecture config of the sampler plan: the UNet's, with the conditioning encoders' geometry taken from the ControlNet."""
         cfg = dict(self.unet.cfg)
@@ -429,6 +500,9 @@ class StableDiffusionBEVControlNetPipeline:
             resample = self._checked_resample()
         if getattr(self, "keep_masks", None) is not None:      # refused or accepted on the host, before anything else of the call
             keep = self._checked_keep_masks(_given_view, height, width)
+        composite = None
+        if getattr(self, "composite_images", None) is not None:   # likewise; its own refusals need the masks to have passed theirs
+            composite = self._checked_composite(_given_view, height, width, output_type)
         if guess_mode:
             # the reference's own guess path cannot run either: under CFG it feeds the ControlNet 5-D `latents` with a 2x-batched camera_param
             # and the un-repeated prompt (pipeline_bev_controlnet.py:366-373) — refused rather than guessed at
@@ -621,10 +695,15 @@ class StableDiffusionBEVControlNetPipeline:
                 with torch.cuda.stream(main):
                     health_dev = torch.cat([pl.health_table() for pl in plans], dim=1).reshape(-1)
         image_rec = [] if (health is not None and output_type != "latent") else None
+        matte_dev, matte = [], None
         if output_type == "latent":
             out, nsfw = latents, None
         else:
-            out = self.decode_latents(latents, **({} if image_rec is None else {"_records": image_rec}))
+            extra = {} if image_rec is None else {"_records": image_rec}
+            if composite is not None:
+                matte_dev = []
+                extra["_composite"] = (composite[0], composite[1], keep.reshape(-1, *keep.shape[2:]), composite[2], matte_dev)
+            out = self.decode_latents(latents, **extra)
             nsfw = None
             if output_type == "pil":
                 out = self.numpy_to_pil_double(out)
@@ -636,7 +715,10 @@ class StableDiffusionBEVControlNetPipeline:
             n_lat = health_dev.numel()
             report = self._sample_health(health, packed[:n_lat].reshape(-1, b * n_cam, 4), b, n_cam,
                                          packed[n_lat:].reshape(b * n_cam, 4) if image_rec else None)
-        result = (out, nsfw) if not return_dict else BEVStableDiffusionPipelineOutput(images=out, nsfw_content_detected=nsfw, health=report)
+        if matte_dev:
+            with torch.cuda.device(device):
+                matte = matte_dev[0].cpu().numpy()
+        result = (out, nsfw) if not return_dict else BEVStableDiffusionPipelineOutput(images=out, nsfw_content_detected=nsfw, health=report, **({} if matte is None else {"matte": matte}))
         if report is not None and self.health_action == "raise" and report.bad_scenes:
             raise SampleHealthError(report.bad_scenes, health=report, output=result)
         return result

@@ -10,6 +10,8 @@ known views: a B x N_cam list of None or (h, w) tensors in [0, 1] — the per-pi
 branch, one ops.LatentBlend behind the scheduler op (StableDiffusionBEVControlNetPipeline.__init__ documents it).
 `pipe.resample = (jump_length, jump_n_sample)` (with keep_masks, DDIM only; default None) resamples such an edit the RePaint way: forward
 jumps with Gaussian noise made on the device (ops.LatentRenoise) between replays of the unchanged step graph (same places document it).
+`pipe.composite_images` / `pipe.composite_feather` (with keep_masks; default None) composite the decoded views with the recorded pictures
+on the device: one ops.ImageComposite behind the VAE decoder, a fully kept pixel is the recorded pixel bit for bit (same places).
 """
 from __future__ import annotations
 

@@ -5,7 +5,7 @@ load a checkpoint in the reference layout, read the training run's hydra overrid
 
   python tools/sample.py --ckpt <ckpt dir with unet/ controlnet/ hydra/overrides.yaml> --sd15 <stable-diffusion-v1-5 dir> \
          --data <folder of *.pth> --out <dir> [key=value overrides as for tools/test.py] [--scheduler unipc|ddim] [--prompt-embeds]
-         [--cond-on-view] [--regenerate-boxes [--region-dilate N] [--resample JL,JN]]
+         [--cond-on-view] [--regenerate-boxes [--region-dilate N] [--resample JL,JN] [--composite [--feather N] [--save-matte]]]
 
 --cond-on-view is demo/run_cond_on_view.py:34-120: the pipe class becomes StableDiffusionBEVControlNetGivenViewPipeline, the ground-truth
 views of every sample (`img` of the `.pth`) are encoded with the pipeline's VAE (`vae.encode(x).latent_dist.mean * scaling_factor`, on
@@ -16,7 +16,13 @@ the HIP kernels), and generation `ti` of the `validation_times - 1` generations 
 boxes (magicdrive_amd.dataset.box_keep_mask: 1 - coverage of each latent pixel by the projected boxes, grown by --region-dilate latent
 pixels, default 1) — lets the sampler regenerate the boxes and keep everything else.  `validation_times` generations, one pipe() call each,
 seeded as the plain loop is (there is no "view ti given" rule), the same files and index.json.  The kept background is the model's own
-last-step output given the known latents, not the encoded input; compositing with the original pictures is left to the caller.
+last-step output given the known latents, not the encoded input; --composite puts the recorded pixels back.
+--composite [--feather N] [--save-matte] (with --regenerate-boxes only) sets pipe.composite_images to the samples' own `img`, mapped from
+[-1, 1] to [0, 1], and pipe.composite_feather = N (image pixels, 0 to 16, default 4): behind the VAE decoder every view becomes
+w * recorded + (1 - w) * generated on the device (ops.ImageComposite; w = dataset.edit_matte of the view's keep mask), so a pixel the
+matte keeps whole is written as the recorded byte.  index.json gains "composite": {"feather": N} and, per generation, `kept_fraction`:
+the mean of the matte per view.  --save-matte writes <scene>_gen<gen>_view<v>_matte.png (8-bit, round(255 w)) next to each view, from
+the rank that sampled the scene.  Without the flag the output is byte for byte what it was.
 --resample JL,JN (with --regenerate-boxes and --scheduler ddim only) sets pipe.resample = (jump_length, jump_n_sample): RePaint resampling,
 which gives the model time to harmonise the regenerated boxes with what is kept at the price of more UNet evaluations per call
 (INTEGRATION.md §1); index.json then carries "resample": [JL, JN].  Without the flag the output is byte for byte what it was.
@@ -156,10 +162,29 @@ def cond_on_view_runs(pipe, kw: Dict, pixel_values: torch.Tensor, run: Dict, gen
         yield ti, (out if full_output else out.images)
 
 
-def regenerate_boxes_inputs(pipe, pixel_values: torch.Tensor, meta: Dict, run: Dict, dilate: int = 1) -> Dict:
+def recorded_pictures(pixel_values: torch.Tensor) -> List[List[torch.Tensor]]:
+    """pixel_values (b, n, 3, H, W) in [-1, 1] -> the B x N_cam list of fp32 (H, W, 3) pictures in [0, 1] that pipe.composite_images takes."""
+    o = (pixel_values.detach().to("cpu", torch.float32) / 2 + 0.5).clamp(0, 1).permute(0, 1, 3, 4, 2).contiguous()
+    return [[o[b, v] for v in range(o.shape[1])] for b in range(o.shape[0])]
+
+
+def save_mattes(out_dir: str, scene: int, gen: int, matte) -> List[str]:
+    """--save-matte: one scene's mattes [n_cam, H, W] in [0, 1] -> <scene>_gen<gen>_view<v>_matte.png, 8-bit grey.  Returns the file names."""
+    import numpy as np
+    from PIL import Image
+    names = []
+    for vi, m in enumerate(np.asarray(matte)):
+        name = f"{scene}_gen{gen}_view{vi}_matte.png"
+        Image.fromarray((np.asarray(m, dtype=np.float32) * 255).round().astype("uint8")).save(os.path.join(out_dir, name))
+        names.append(name)
+    return names
+
+
+def regenerate_boxes_inputs(pipe, pixel_values: torch.Tensor, meta: Dict, run: Dict, dilate: int = 1, composite=None) -> Dict:
     """--regenerate-boxes, per batch: every ground-truth view encoded (encode_given_views) and given, and pipe.keep_masks set from each
     sample's own boxes — project_box_corners with the sample's lidar2image / img_aug_matrix, box_keep_mask at the run's image size and the
-    latents' (h, w).  Returns the extra keyword arguments of the batch's pipe() calls: {conditional_latents}."""
+    latents' (h, w).  composite (--composite: the feather, or None): pipe.composite_images = the same views as pictures in [0, 1] and
+    pipe.composite_feather.  Returns the extra keyword arguments of the batch's pipe() calls: {conditional_latents}."""
     from magicdrive_amd.dataset import box_keep_mask, project_box_corners
     if pixel_values is None:
         raise ValueError("--regenerate-boxes needs the ground-truth views (`img`) in the samples")
@@ -171,6 +196,8 @@ def regenerate_boxes_inputs(pipe, pixel_values: torch.Tensor, meta: Dict, run: D
         masks.append(list(box_keep_mask(corners, kept, tuple(run["image_size"]), tuple(latents.shape[-2:]), dilate=dilate)))
     assert len(masks) == bs and all(len(m) == n_cam for m in masks)
     pipe.keep_masks = masks
+    if composite is not None:
+        pipe.composite_images, pipe.composite_feather = recorded_pictures(pixel_values), int(composite)
     return dict(conditional_latents=[[latents[b, v] for v in range(n_cam)] for b in range(bs)])
 
 
@@ -306,6 +333,10 @@ def main(argv=None):
     ap.add_argument("--region-dilate", type=int, default=1, help="--regenerate-boxes: grow the regenerated region by N latent pixels (default 1)")
     ap.add_argument("--resample", default=None, metavar="JL,JN", help="--regenerate-boxes with --scheduler ddim: RePaint resampling, pipe.resample = (jump_length, "
                     "jump_n_sample), two integers >= 1 (INTEGRATION.md §1); recorded in index.json")
+    ap.add_argument("--composite", action="store_true", help="--regenerate-boxes: composite every view with the sample's recorded picture on the device "
+                    "(pipe.composite_images, INTEGRATION.md §1): pixels the matte keeps whole are the recorded bytes; index.json gains composite / kept_fraction")
+    ap.add_argument("--feather", type=int, default=None, metavar="N", help="--composite: pipe.composite_feather, the matte's erosion and blur radius in image pixels, 0 to 16 (default 4)")
+    ap.add_argument("--save-matte", action="store_true", help="--composite: write <scene>_gen<gen>_view<v>_matte.png (8-bit) next to each view")
     ap.add_argument("--box-bucket", type=int, default=None, help="one sampler plan per bucket of N padded box counts (pipe.box_bucket, INTEGRATION.md §1): the "
                     "padded box count changes with almost every batch of a validation run; default: an exact plan per count")
     ap.add_argument("--scene-boxes", action="store_true", help="every scene of a batch attends to its own boxes only (pipe.scene_boxes, INTEGRATION.md §1): "
@@ -336,6 +367,15 @@ def main(argv=None):
         if len(parts) != 2 or not all(p_.strip().isdigit() and int(p_) >= 1 for p_ in parts):
             raise SystemExit(f"--resample {a.resample!r}: JL,JN, two integers >= 1")
         resample = (int(parts[0]), int(parts[1]))
+    if a.composite and not a.regenerate_boxes:
+        raise SystemExit("--composite puts the recorded pictures back around a kept-region edit: it is valid with --regenerate-boxes only")
+    if (a.feather is not None or a.save_matte) and not a.composite:
+        raise SystemExit("--feather and --save-matte belong to --composite")
+    feather = None
+    if a.composite:
+        feather = 4 if a.feather is None else a.feather
+        if not 0 <= feather <= 16:
+            raise SystemExit(f"--feather {feather}: an integer number of image pixels in [0, 16]")
     given_view = a.cond_on_view or a.regenerate_boxes
     if a.pipe_factory:
         import importlib
@@ -393,7 +433,7 @@ def main(argv=None):
                         images_out.append(views)
             else:
                 if a.regenerate_boxes:                  # every view given, masked by the sample's boxes; the loop below is the plain one
-                    kw = dict(kw, **regenerate_boxes_inputs(pipe, pixel_values, meta, run, a.region_dilate))
+                    kw = dict(kw, **regenerate_boxes_inputs(pipe, pixel_values, meta, run, a.region_dilate, composite=feather))
                 for ti in range(run["validation_times"]):
                     g = gen
                     if a.reseed_per_run and base_gen is not None:
@@ -403,6 +443,10 @@ def main(argv=None):
                     for bi, views in enumerate(out.images):                       # List[List[PIL]]: scene x view
                         records.append(dict(scene=scene0 + bi, gen=ti, rank=rank, seed=seed, **(health_fields(out.health, bi) if health_on else {})))
                         images_out.append(views)
+                        if feather is not None:
+                            records[-1]["kept_fraction"] = [float(m.mean()) for m in out.matte[bi]]
+                            if a.save_matte and not (a.health == "skip" and records[-1].get("ok") is False):
+                                save_mattes(a.out, scene0 + bi, ti, out.matte[bi])
             n_local += bs
         n_bad_local += sum(1 for r_ in records if r_.get("ok") is False)
         index += exchange_batch(records, images_out, rank, world, a.gather_images, a.out, skip_bad=a.health == "skip")
@@ -410,6 +454,7 @@ def main(argv=None):
         index.sort(key=lambda r_: (r_["scene"], r_["gen"]))
         with open(os.path.join(a.out, "index.json"), "w") as f:
             json.dump(dict(world=world, seed=run["seed"], gather_images=bool(a.gather_images), **({} if resample is None else {"resample": list(resample)}),
+                           **({} if feather is None else {"composite": {"feather": feather}}),
                            generations=index), f, indent=1)
         print(f"sampled {len(data)} scenes x {run['validation_times'] - (1 if a.cond_on_view else 0)} on {world} rank(s) -> {a.out}")
     n_bad = n_bad_local
