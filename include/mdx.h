@@ -404,7 +404,8 @@ int mdx_timestep_embedding(const MdxTimeEmbDesc* d, void* stream);
  * Requirements (MDX_EINVAL; the same hold for mdx_cfg_unipc_step): x, eps, coef, step_ptr 4-byte aligned; xin_c, xin_ld, gv_last_step fit a
  * 32-bit int; xin_ld is not negative; x_in at its element's alignment (4 / 2 bytes); xin_ld > 0 needs 0 < xin_c <= xin_ld and xin_c
  * dividing n; a given-view mode needs gv_noise (mode 1: also gv_cond) and gv_view_elems dividing n.  The x_in clauses are one check for
- * every op that refreshes x_in (these two, mdx_latent_blend_*, mdx_latent_renoise_*): same rule, same message behind the op's name.
+ * every op that refreshes x_in (these two, mdx_cfg_ddim_eta_step_*, mdx_latent_blend_*, mdx_latent_renoise_*): same rule, same message behind
+ * the op's name.
  */
 typedef struct MdxDdimDesc {
     float* x; const float* eps; const float* coef; int32_t* step_ptr; void* x_in; void* reserved_p;
@@ -603,6 +604,56 @@ typedef struct MdxRenoiseDesc {
 int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream);
 
 /*
+ * mdx_cfg_ddim_eta_step_bf16 / _f16 — the DDIM step with eta > 0: classifier-free guidance, the DDIM update, the variance noise of
+ * scheduling_ddim.py:415-438, the given views and the x_in refresh in one pass, with the noise made on the device (additive symbols, the
+ * ABI version stays 12; MDX_OP_DDIM_ETA; csrc/noise.hip; mdx_last_kernel() starts with "ddim_eta_kernel").  It stands in the place of
+ * mdx_cfg_ddim_step in a step program; mdx_cfg_ddim_step itself is unchanged.  The two builds differ only in the 16-bit type of x_in.
+ *   x, eps, coef, step_ptr, x_in, cfg, guidance, xin_c, xin_ld, gv_* : as in MdxDdimDesc; coef is the UNCHANGED table of 4 columns;
+ *   var       : fp32 [n_rows][2] = {dir, std} per step: std = eta sqrt(variance), dir = sqrt(1 - a_prev - std^2) (eta = 0: dir = coef[.][3]);
+ *   draw_ptr  : int32, how many steps of this op have run in this call, READ AND WRITTEN;
+ *   seeds     : uint64 [n / group_elems], device memory: one seed per group of group_elems consecutive elements (a view);   or
+ *   noise     : fp32 [n], the caller's own standard normal noise (DDIMScheduler.step's variance_noise); when not NULL it is z and seeds
+ *               is not read.
+ * With s = *step_ptr and v = *draw_ptr, both read when the kernel RUNS (a replayed hipGraph sees the current values), c = coef + 4 s and
+ * (dir, std) = var[s], for every i < n:
+ *   e   = cfg != 0 ? eps[i] + guidance (eps[n + i] - eps[i]) : eps[i];      a given element under gv_mode 2: e = gv_noise[i]
+ *   x0  = (x[i] - c[1] e) / c[0];   det = c[2] x0 + dir e                    a given element under gv_mode 2: dir = c[3], std = 0
+ *   xn  = std != 0 ? det + (std * z[i]) : det                                the product std * z[i] is rounded before it is added
+ *   x[i] = gv_mode 1, given, s < gv_last_step ? c[2] gv_cond[i] + c[3] gv_noise[i] : xn
+ * and every written element refreshes x_in as mdx_cfg_ddim_step does.  A gv_mode 2 element therefore stays exactly on its own add_noise
+ * trajectory.  A row with std == 0 computes no noise and, with dir = c[3], gives the bits of mdx_cfg_ddim_step on the same operands.
+ * Then a separate one-thread launch (every block of the first has read the counters by then) sets *step_ptr = s + 1, *draw_ptr = v + 1.
+ * Out of range — s < 0 or s >= n_rows — is a caller error discovered on the device: x is filled with NaN, x_in and both counters are
+ * left alone.
+ * The generated noise z, to the bit of its inputs: the mapping of mdx_latent_renoise_* with counter word 3 = 1.  Element i belongs to
+ * group g = i / group_elems with relative index e = i - g * group_elems; one Philox4x32-10 call with counter
+ * (lo32(e / 4), hi32(e / 4), v, 1) and key (lo32(seeds[g]), hi32(seeds[g])) yields (w0, w1, w2, w3) for four consecutive e, and
+ * u1, u2 and z[4k + 0 .. 3] follow from the words exactly as there (fp32 evaluation, within 1e-5 of the exact value).  Counter word 3 is
+ * the stream's domain: 0 = a jump of mdx_latent_renoise_*, 1 = a step of this op.  Philox is a bijection of the counter under one key,
+ * so the two streams never share a block, even with equal seed, equal element and v equal to the jump's visit count: one seed per scene
+ * serves both.  A resample jump moves *step_ptr back and leaves *draw_ptr alone: a revisited step draws fresh noise.
+ * fp32 math, no atomics, 64-bit addressing.  16-byte accesses of x when x is 16-byte aligned and group_elems % 4 == 0; any other case is
+ * SERVED by scalar accesses with the same bits.  Nothing is read or written past n elements of x / noise / gv_cond / gv_noise, n (2 n
+ * when cfg != 0) of eps, n / group_elems seeds, n / gv_view_elems mask bytes, or the x_in pixels of n / xin_c rows (twice when cfg != 0).
+ * Contract, checked on the host before the launch (MDX_EINVAL, the message names the field): x, eps, coef, var, step_ptr, draw_ptr not
+ * NULL (x_in may be NULL); seeds and noise not both NULL; x, eps, coef, var, step_ptr, draw_ptr, noise 4-byte aligned, seeds 8-byte
+ * aligned, x_in at its element's alignment (4 / 2 bytes); n not negative; group_elems >= 1 and divides n; n_rows fits a 32-bit int and
+ * is >= 1; cfg in {0, 1}; xin_c, xin_ld, gv_last_step fit a 32-bit int and xin_ld is not negative; xin_ld > 0 needs
+ * 0 < xin_c <= xin_ld and xin_c dividing n; a given-view mode needs gv_noise (mode 1: also gv_cond) and gv_view_elems dividing n.
+ * n == 0: MDX_OK (after the checks), nothing is launched.
+ */
+typedef struct MdxDdimEtaDesc {
+    float* x; const float* eps; const float* coef; const float* var; int32_t* step_ptr; int32_t* draw_ptr; void* x_in;
+    const uint64_t* seeds; const float* noise;
+    int64_t n, cfg;
+    double guidance;
+    int64_t xin_c, xin_ld, group_elems, n_rows;
+    const float* gv_cond; const float* gv_noise; const uint8_t* gv_mask;
+    int64_t gv_mode, gv_view_elems, gv_last_step;
+} MdxDdimEtaDesc;
+int mdx_cfg_ddim_eta_step_bf16(const MdxDdimEtaDesc* d, void* stream);
+
+/*
  * mdx_image_composite_bf16 / _f16 — composite a kept-region edit with the recorded pictures: every pixel outside the edited regions
  * becomes the recorded pixel again, bit for bit, and a feathered band inside the kept region hides the seam (additive symbols, the ABI
  * version stays 12; MDX_OP_IMAGE_COMPOSITE; csrc/composite.hip; mdx_last_kernel() starts with "composite_kernel").  An op on the VAE
@@ -666,6 +717,7 @@ int mdx_image_composite_bf16(const MdxCompositeDesc* d, void* stream);
 #define MDX_OP_LATENT_BLEND 18         /* MdxBlendDesc through mdx_latent_blend_* */
 #define MDX_OP_LATENT_RENOISE 19       /* MdxRenoiseDesc through mdx_latent_renoise_* */
 #define MDX_OP_IMAGE_COMPOSITE 20      /* MdxCompositeDesc through mdx_image_composite_* */
+#define MDX_OP_DDIM_ETA 21             /* MdxDdimEtaDesc through mdx_cfg_ddim_eta_step_* */
 
 /* 16-bit storage / MFMA operand type of an op's activations and weights.  The reference samples in fp16 (magicdrive/misc/test_utils.py:95
  * `weight_dtype = torch.float16`); BASELINE.json's benchmark configuration names bf16.  Every op entry point exists in both builds:
@@ -702,6 +754,7 @@ int mdx_sdpa_f16(const MdxSdpaDesc* d, void* stream);
 int mdx_latent_blend_f16(const MdxBlendDesc* d, void* stream);
 int mdx_latent_renoise_f16(const MdxRenoiseDesc* d, void* stream);
 int mdx_image_composite_f16(const MdxCompositeDesc* d, void* stream);
+int mdx_cfg_ddim_eta_step_f16(const MdxDdimEtaDesc* d, void* stream);
 
 /* Run ops[0..n) in order on `stream`.  Stops at the first failing op (returns its code;
  * mdx_last_error() names the op index followed by the op's own message).  Every op goes through the entry point of its dtype, so each

@@ -25,6 +25,7 @@ OP_SDPA = 17                          # MdxSdpaDesc through mdx_sdpa_*: flash at
 OP_LATENT_BLEND = 18                  # MdxBlendDesc through mdx_latent_blend_*: per-pixel keep masks behind the scheduler op (csrc/blend.hip)
 OP_LATENT_RENOISE = 19                # MdxRenoiseDesc through mdx_latent_renoise_*: a forward jump with device-side Gaussian noise (csrc/noise.hip)
 OP_IMAGE_COMPOSITE = 20               # MdxCompositeDesc through mdx_image_composite_*: kept-region edits composited with the recorded pictures (csrc/composite.hip)
+OP_DDIM_ETA = 21                      # MdxDdimEtaDesc through mdx_cfg_ddim_eta_step_*: the DDIM step with eta > 0, variance noise made on the device (csrc/noise.hip)
 OP_BYTES = 512
 
 EPI_NONE, EPI_GEGLU, EPI_SILU = 0, 1, 2
@@ -66,6 +67,8 @@ MdxStatsDesc = _struct("MdxStatsDesc", _f(P, "X out row_dev") + _f(I, "G n sG n_
 MdxSdpaDesc = _struct("MdxSdpaDesc", _f(P, "Q K V O klen_dev") + _f(I, "B H Tq Tk d ldq sQ ldk sK ldv sV ldo sO") + _f(D, "scale") + _f(I, "causal"))
 MdxBlendDesc = _struct("MdxBlendDesc", _f(P, "x cond noise mask coef step_ptr x_in") + _f(I, "n mask_elems coef_ld col_a col_s last_step cfg xin_c xin_ld"))
 MdxRenoiseDesc = _struct("MdxRenoiseDesc", _f(P, "x x_in coef step_ptr visit_ptr seeds") + _f(I, "n group_elems jump n_rows coef_ld col_t col_p cfg xin_c xin_ld"))
+MdxDdimEtaDesc = _struct("MdxDdimEtaDesc", _f(P, "x eps coef var step_ptr draw_ptr x_in seeds noise") + _f(I, "n cfg") + _f(D, "guidance")
+                         + _f(I, "xin_c xin_ld group_elems n_rows") + _f(P, "gv_cond gv_noise gv_mask") + _f(I, "gv_mode gv_view_elems gv_last_step"))
 MdxCompositeDesc = _struct("MdxCompositeDesc", _f(P, "gen orig keep out matte has") + _f(I, "V C H W f feather gen_f32 g_sv g_sc g_ld"))
 DESC_OF_OP = {
     OP_GEMM: MdxGemmDesc, OP_CONV: MdxConvDesc, OP_CONV_DIRECT: MdxConvDirectDesc, OP_ATTN: MdxAttnDesc,
@@ -78,6 +81,7 @@ DESC_OF_OP = {
 # OP_LATENT_BLEND takes MdxBlendDesc, likewise; its contract rows are tests/test_latent_blend_contract.py.
 # OP_LATENT_RENOISE takes MdxRenoiseDesc, likewise; its contract rows are tests/test_latent_renoise_contract.py.
 # OP_IMAGE_COMPOSITE takes MdxCompositeDesc, likewise; its contract rows are tests/test_composite_contract.py.
+# OP_DDIM_ETA takes MdxDdimEtaDesc, likewise; its contract rows are tests/test_ddim_eta_contract.py.
 DTYPE_BF16, DTYPE_F16 = 0, 1          # MdxOp.dtype: the 16-bit storage / MFMA operand type of an op (mdx.h)
 ENTRY_OF_OP = {
     OP_GEMM: "mdx_gemm_bf16", OP_CONV: "mdx_conv2d_bf16", OP_CONV_DIRECT: "mdx_conv2d_direct", OP_ATTN: "mdx_attention_bf16",
@@ -91,6 +95,7 @@ ENTRY_OF_OP = {
     OP_LATENT_BLEND: "mdx_latent_blend_bf16",
     OP_LATENT_RENOISE: "mdx_latent_renoise_bf16",
     OP_IMAGE_COMPOSITE: "mdx_image_composite_bf16",
+    OP_DDIM_ETA: "mdx_cfg_ddim_eta_step_bf16",
 }
 def entry_name(opcode: int, dtype: int = DTYPE_BF16) -> str:
     """C entry point of an op in the bf16 or the fp16 build (mdx_gemm_bf16 -> mdx_gemm_f16, mdx_elementwise -> mdx_elementwise_f16)."""
@@ -111,7 +116,7 @@ class MdxOp(C.Structure):
 
 
 assert C.sizeof(MdxOp) == OP_BYTES
-for _d in list(DESC_OF_OP.values()) + [MdxStatsDesc, MdxSdpaDesc, MdxBlendDesc, MdxRenoiseDesc, MdxCompositeDesc]:
+for _d in list(DESC_OF_OP.values()) + [MdxStatsDesc, MdxSdpaDesc, MdxBlendDesc, MdxRenoiseDesc, MdxCompositeDesc, MdxDdimEtaDesc]:
     assert C.sizeof(_d) <= OP_BYTES - 16 and C.sizeof(_d) % 8 == 0
 
 

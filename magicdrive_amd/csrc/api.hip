@@ -114,6 +114,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
             case MDX_OP_LATENT_BLEND: return mdx_latent_blend_f16((const MdxBlendDesc*)d, st);
             case MDX_OP_LATENT_RENOISE: return mdx_latent_renoise_f16((const MdxRenoiseDesc*)d, st);
             case MDX_OP_IMAGE_COMPOSITE: return mdx_image_composite_f16((const MdxCompositeDesc*)d, st);
+            case MDX_OP_DDIM_ETA: return mdx_cfg_ddim_eta_step_f16((const MdxDdimEtaDesc*)d, st);
             default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
         }
     }
@@ -139,6 +140,7 @@ static int run_op(const MdxOp* op, hipStream_t st) {
         case MDX_OP_LATENT_BLEND: return mdx_latent_blend_bf16((const MdxBlendDesc*)d, st);
         case MDX_OP_LATENT_RENOISE: return mdx_latent_renoise_bf16((const MdxRenoiseDesc*)d, st);
         case MDX_OP_IMAGE_COMPOSITE: return mdx_image_composite_bf16((const MdxCompositeDesc*)d, st);
+        case MDX_OP_DDIM_ETA: return mdx_cfg_ddim_eta_step_bf16((const MdxDdimEtaDesc*)d, st);
         default: return set_error(MDX_EINVAL, "unknown opcode %ld", (long)op->opcode);
     }
 }

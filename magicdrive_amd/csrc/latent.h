@@ -1,5 +1,6 @@
-// latent.h — what the ops that update the sampler's latents share (mdx_cfg_ddim_step, mdx_cfg_unipc_step, mdx_latent_blend_*,
-// mdx_latent_renoise_*): the refresh of the network's input copy x_in and, for the two scheduler ops, the CFG combine and the given views.
+// latent.h — what the ops that update the sampler's latents share (mdx_cfg_ddim_step, mdx_cfg_unipc_step, mdx_cfg_ddim_eta_step_*,
+// mdx_latent_blend_*, mdx_latent_renoise_*): the refresh of the network's input copy x_in and, for the three scheduler ops, the CFG combine
+// and the given views.
 // ONE copy of each expression (as renoise_f in common.h), on the device and in the host checks: a new latent op embeds an XinDst in its
 // kernel parameters, calls need_xin / xin_of in its entry point and store_xin in its kernel.
 #pragma once

@@ -27,6 +27,7 @@
 #define mdx_sdpa_bf16 mdx_sdpa_f16
 #define mdx_latent_blend_bf16 mdx_latent_blend_f16
 #define mdx_latent_renoise_bf16 mdx_latent_renoise_f16
+#define mdx_cfg_ddim_eta_step_bf16 mdx_cfg_ddim_eta_step_f16
 #define mdx_image_composite_bf16 mdx_image_composite_f16
 #endif
 

@@ -1,4 +1,6 @@
-// noise.hip — mdx_latent_renoise_*: one forward jump of the sampler with noise made on the device (MdxRenoiseDesc, include/mdx.h).
+// noise.hip — the two ops whose Gaussian noise is made on the device (philox.h): mdx_latent_renoise_* (below) and mdx_cfg_ddim_eta_step_*
+// (the DDIM step with eta > 0, further down).
+// mdx_latent_renoise_*: one forward jump of the sampler with noise made on the device (MdxRenoiseDesc, include/mdx.h).
 //
 // RePaint resampling (Lugmayr et al. 2022) diffuses the sample forward again by `jump` steps with fresh noise and takes the same reverse
 // steps once more.  With c = *step_ptr and v = *visit_ptr, read when the kernel runs (a replayed hipGraph sees the current values):
@@ -23,6 +25,7 @@
 #include "common.h"
 #include "launch.h"
 #include "latent.h"
+#include "philox.h"
 
 namespace mdx {
 
@@ -32,26 +35,6 @@ struct RenoiseParams { float* x; const float* coef; int* step; int* visit; const
                        long group, bpg; int jump, n_rows, coef_ld, col_t, col_p; XinDst xin; };
 
 __device__ __forceinline__ bool renoise_in_range(int c, int jump, int n_rows) { return jump >= 1 && c >= 1 && c <= n_rows && c - jump >= 0; }
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned w[4]) {
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-// u1 = ((wa >> 8) + 1) 2^-24 in (0, 1], u2 = (wb >> 8) 2^-24 in [0, 1), both exact; (za, zb) = sqrt(-2 ln u1) (cos, sin)(2 pi u2)
-__device__ __forceinline__ void box_muller(unsigned wa, unsigned wb, float& za, float& zb) {
-    const float u1 = (float)((wa >> 8) + 1u) * 0x1p-24f, u2 = (float)(wb >> 8) * 0x1p-24f;
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincospif(2.0f * u2, &sn, &cs);
-    za = rad * cs; zb = rad * sn;
-}
 
 __device__ __forceinline__ float renoise_value(float r, float sg, float x, float z) {
     float nz = sg * z;
@@ -77,11 +60,8 @@ __global__ __launch_bounds__(RN_T) void renoise_kernel(RenoiseParams p) {
     const float r = tgt / cur;
     const float sg = sqrtf(fmaxf(0.0f, __builtin_fmaf(-r, r, 1.0f)));    // 1 - r r with ONE rounding, pinned (it cancels when r is near 1)
     const unsigned long long seed = p.seeds[g];
-    unsigned w[4];
-    philox4x32_10((unsigned)(unsigned long long)k, (unsigned)((unsigned long long)k >> 32), (unsigned)v, 0u, (unsigned)seed, (unsigned)(seed >> 32), w);
     float z[4];
-    box_muller(w[0], w[1], z[0], z[1]);
-    box_muller(w[2], w[3], z[2], z[3]);
+    noise_block(seed, k, (unsigned)v, MDX_NOISE_DOMAIN_RENOISE, z);
     if (VEC) {
         const float4 x = *reinterpret_cast<const float4*>(p.x + i0);
         float4 y;
@@ -111,9 +91,130 @@ __global__ void renoise_counters_kernel(int* step, int* visit, int jump, int n_r
     *visit += 1;
 }
 
+// ---- mdx_cfg_ddim_eta_step_*: the DDIM step with eta > 0 (MdxDdimEtaDesc, include/mdx.h) ------------------------------------------------
+// ddim_kernel's update (elementwise.hip) plus the variance noise of scheduling_ddim.py:415-438, in one pass.  With s = *step_ptr and
+// v = *draw_ptr read when the kernel runs, c = coef[s] (the UNCHANGED 4-column table) and (dir, sd) = var[s]:
+//     e = cfg_eps(...), x0 = (x - c[1] e) / c[0], det = c[2] x0 + dir e, xn = sd != 0 ? det + rounded(sd z) : det, xn = gv_renoise(xn)
+// A given element under gv_mode 2 takes e = gv_noise, dir = c[3] and no noise: it stays on its own add_noise trajectory.  z is noise[i]
+// when the caller brings its own (variance_noise), else the block of philox.h with counter word 2 = v in the domain of this op: the
+// renoise mapping with counter word 3 = 1.  sd == 0: no Philox is computed and the row's update is det — with dir = c[3], ddim_kernel's
+// bits (the same expressions under the same flags).  The two instances are renoise_kernel's: one thread per four relative indices.
+struct DdimEtaParams { float* x; const float* eps; const float* coef; const float* var; int* step; int* draw; const unsigned long long* seeds;
+                       const float* noise; long group, bpg; int n_rows; float g; XinDst xin; GivenViews gv; };
+
+__device__ __forceinline__ bool ddim_eta_in_range(int s, int n_rows) { return s >= 0 && s < n_rows; }
+
+__device__ __forceinline__ float ddim_eta_value(const DdimEtaParams& p, const float* c, float dir, float sd, int step, long i, float x, float z) {
+    float e = cfg_eps(p.eps, p.xin.n, p.xin.cfg, p.g, i);
+    const bool given = gv_given(p.gv, i);
+    if (given && p.gv.mode == 2) { e = p.gv.noise[i]; dir = c[3]; sd = 0.0f; }
+    float x0 = (x - c[1] * e) / c[0];
+    float det = c[2] * x0 + dir * e;
+    asm("" : "+v"(det));                                       // det is ddim_kernel's value before anything is added to it
+    float xn = det;
+    if (sd != 0.0f) {
+        float nz = sd * z;
+        asm("" : "+v"(nz));                                    // a rounded product in both instances (renoise_value's pattern)
+        xn = det + nz;
+    }
+    return gv_renoise(p.gv, given, step, i, c[2], c[3], xn);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(RN_T) void ddim_eta_kernel(DdimEtaParams p) {
+    const int s = *p.step, v = *p.draw;
+    const long q = (long)blockIdx.x * RN_T + threadIdx.x;
+    const long g = q / p.bpg;
+    if (g >= p.xin.n / p.group) return;
+    const long k = q - g * p.bpg;
+    const long e0 = 4 * k;
+    const long i0 = g * p.group + e0;
+    const int cnt = VEC ? 4 : (int)(p.group - e0 < 4 ? p.group - e0 : 4);
+    if (!ddim_eta_in_range(s, p.n_rows)) {                      // uniform over the launch: poison x, touch nothing else
+        for (int j = 0; j < cnt; ++j) p.x[i0 + j] = __builtin_nanf("");
+        return;
+    }
+    const float* c = p.coef + 4 * (long)s;
+    const float dir = p.var[2 * (long)s], sd = p.var[2 * (long)s + 1];
+    float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (sd != 0.0f) {                                           // uniform over the launch
+        if (p.noise) {
+            for (int j = 0; j < cnt; ++j) z[j] = p.noise[i0 + j];
+        } else {
+            noise_block(p.seeds[g], k, (unsigned)v, MDX_NOISE_DOMAIN_DDIM_ETA, z);
+        }
+    }
+    if (VEC) {
+        const float4 x = *reinterpret_cast<const float4*>(p.x + i0);
+        float4 y;
+        y.x = ddim_eta_value(p, c, dir, sd, s, i0, x.x, z[0]);
+        y.y = ddim_eta_value(p, c, dir, sd, s, i0 + 1, x.y, z[1]);
+        y.z = ddim_eta_value(p, c, dir, sd, s, i0 + 2, x.z, z[2]);
+        y.w = ddim_eta_value(p, c, dir, sd, s, i0 + 3, x.w, z[3]);
+        *reinterpret_cast<float4*>(p.x + i0) = y;
+        store_xin(p.xin, i0, y.x); store_xin(p.xin, i0 + 1, y.y); store_xin(p.xin, i0 + 2, y.z); store_xin(p.xin, i0 + 3, y.w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j < cnt) {
+                const float y = ddim_eta_value(p, c, dir, sd, s, i0 + j, p.x[i0 + j], z[j]);
+                p.x[i0 + j] = y;
+                store_xin(p.xin, i0 + j, y);
+            }
+        }
+    }
+}
+
+// behind ddim_eta_kernel on the same stream: both counters move only when the step was taken
+__global__ void ddim_eta_counters_kernel(int* step, int* draw, int n_rows) {
+    if (!ddim_eta_in_range(*step, n_rows)) return;
+    *step += 1;
+    *draw += 1;
+}
+
 }  // namespace mdx
 
 using namespace mdx;
+
+extern "C" int mdx_cfg_ddim_eta_step_bf16(const MdxDdimEtaDesc* d, void* stream) {
+#if MDX_F16
+    const char* op = "mdx_cfg_ddim_eta_step_f16";
+#else
+    const char* op = "mdx_cfg_ddim_eta_step";
+#endif
+    if (!d) return set_error(MDX_EINVAL, "%s: null descriptor", op);
+    if (!d->x) return set_error(MDX_EINVAL, "%s: x must not be NULL", op);
+    if (!d->eps) return set_error(MDX_EINVAL, "%s: eps must not be NULL", op);
+    if (!d->coef) return set_error(MDX_EINVAL, "%s: coef must not be NULL", op);
+    if (!d->var) return set_error(MDX_EINVAL, "%s: var must not be NULL", op);
+    if (!d->step_ptr) return set_error(MDX_EINVAL, "%s: step_ptr must not be NULL", op);
+    if (!d->draw_ptr) return set_error(MDX_EINVAL, "%s: draw_ptr must not be NULL", op);
+    if (!d->seeds && !d->noise) return set_error(MDX_EINVAL, "%s: seeds must not be NULL when noise is (one of the two makes z)", op);
+    MDX_NEED(need_aligned(op, "x", d->x, 4)); MDX_NEED(need_aligned(op, "eps", d->eps, 4)); MDX_NEED(need_aligned(op, "coef", d->coef, 4));
+    MDX_NEED(need_aligned(op, "var", d->var, 4)); MDX_NEED(need_aligned(op, "step_ptr", d->step_ptr, 4)); MDX_NEED(need_aligned(op, "draw_ptr", d->draw_ptr, 4));
+    MDX_NEED(need_aligned(op, "seeds", d->seeds, 8)); MDX_NEED(need_aligned(op, "noise", d->noise, 4));
+    MDX_NEED(need_int(op, "n_rows", d->n_rows)); MDX_NEED(need_int(op, "gv_last_step", d->gv_last_step));
+    if (d->n < 0) return set_error(MDX_EINVAL, "%s: n=%ld must not be negative", op, (long)d->n);
+    if (d->group_elems < 1 || d->n % d->group_elems) return set_error(MDX_EINVAL, "%s: group_elems=%ld must be >= 1 and divide n=%ld", op, (long)d->group_elems, (long)d->n);
+    if (d->n_rows < 1) return set_error(MDX_EINVAL, "%s: n_rows=%ld must be >= 1", op, (long)d->n_rows);
+    if (d->cfg != 0 && d->cfg != 1) return set_error(MDX_EINVAL, "%s: cfg=%ld must be 0 or 1", op, (long)d->cfg);
+    MDX_NEED(need_xin(op, d));
+    MDX_NEED(need_given_views(op, d));
+    if (d->n == 0) return MDX_OK;
+    const long bpg = (long)((d->group_elems + 3) / 4);           // blocks of four relative indices per group; the last may be partial
+    DdimEtaParams p{d->x, d->eps, d->coef, d->var, d->step_ptr, d->draw_ptr, (const unsigned long long*)d->seeds, d->noise, d->group_elems, bpg,
+                    (int)d->n_rows, (float)d->guidance, xin_of(d), given_views_of(d)};
+    const bool vec = ((uintptr_t)d->x & 15) == 0 && d->group_elems % 4 == 0;
+    const long work = (d->n / p.group) * bpg;
+    const long blocks = (work + RN_T - 1) / RN_T;
+    if (blocks > 0x7fffffffL) return set_error(MDX_EINVAL, "%s: n=%ld needs more than 2^31 - 1 workgroups", op, (long)d->n);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL((ddim_eta_kernel<true>), dim3((unsigned)blocks), dim3(RN_T), 0, st, p);
+    else hipLaunchKernelGGL((ddim_eta_kernel<false>), dim3((unsigned)blocks), dim3(RN_T), 0, st, p);
+    MDX_NEED(check_launch(vec ? "ddim_eta_kernel" : "ddim_eta_kernel_scalar"));
+    hipLaunchKernelGGL(ddim_eta_counters_kernel, dim3(1), dim3(1), 0, st, p.step, p.draw, p.n_rows);
+    return check_launch("ddim_eta_counters_kernel", false);
+}
 
 extern "C" int mdx_latent_renoise_bf16(const MdxRenoiseDesc* d, void* stream) {
 #if MDX_F16

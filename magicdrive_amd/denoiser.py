@@ -299,7 +299,7 @@ class SamplerPlan:
     def __init__(self, cfg, unet: PackedNet, cn: PackedNet, device, b: int, do_cfg: bool, L_box: int, latent_hw=(28, 50),
                  num_steps: int = 50, guidance_scale: float = 2.0, conditioning_scale: float = 1.0, n_text: int = 77,
                  scheduler_kind: str = "ddim", given_view_mode: int = 0, fork: bool = False, dynamic_boxes=False, health=None, keep_regions: bool = False,
-                 resample: Optional[int] = None):
+                 resample: Optional[int] = None, stochastic: bool = False):
         """dynamic_boxes: L_box is a box CAPACITY; one plan (and one captured graph) then serves every call whose boxes are padded to
         1 .. L_box: the prologue (box MLP, attn2 to_k / to_v) runs at capacity, and every text-context attention reads its key count
         from cond.live on the device.  Self and cross-view attention are untouched.
@@ -320,7 +320,14 @@ class SamplerPlan:
           diffused forward again by `resample` steps with noise made on the device, step_ctr moves back by as many (time embeddings,
           scheduler row, blend and health trace all select by it), visit_ctr moves on.  The caller launches it between steps
           (schedulers.resample_actions; launch_jump).  The step program is unchanged, op for op.  UniPC is refused: its multistep history
-          (x_last, m1, m2) belongs to the trajectory a jump abandons.  None (default): nothing is allocated or built."""
+          (x_last, m1, m2) belongs to the trajectory a jump abandons.  None (default): nothing is allocated or built.
+        stochastic (scheduler_kind "ddim" only): DDIM with eta > 0.  ops.DdimEtaStep stands in the scheduler op's place (same fields, same
+          given views); every other op of the step program, the prologue and the jump program are unchanged: blend, jump and health
+          trace read the unchanged 4-column table.  The plan owns var (fp32 [num_steps, 2] = (dir, std) per step, written by load_inputs:
+          eta's VALUE is data, one captured plan serves every eta > 0), draw_ctr (int32 [1], zeroed by load_inputs; a jump moves
+          step_ctr back and leaves it alone, so a revisited step draws fresh noise) and seeds (int64 [b * n_cam], one per view) — the
+          tensor a resample plan already owns: with both switches on there is ONE, and the noise domain separates the two streams.
+          False (default): nothing is allocated or built."""
         self.cfg, self.device = cfg, device
         assert health in (None, "final", "trace"), f"health={health!r}: None, 'final' or 'trace'"
         self.health = health
@@ -336,6 +343,8 @@ class SamplerPlan:
         assert resample is None or keep_regions, "resample harmonises a kept-region edit: it needs keep_regions"
         assert resample is None or scheduler_kind == "ddim", "resample is DDIM-only: UniPC's multistep history does not survive a jump"
         self.resample = resample
+        assert not stochastic or scheduler_kind == "ddim", "stochastic is DDIM with eta > 0: UniPC has no variance noise"
+        self.stochastic = bool(stochastic)
         self.scheduler_kind = scheduler_kind
         self.given_view_mode = given_view_mode
         n_cam = len(cfg["neighboring_view_pair"])
@@ -365,6 +374,11 @@ class SamplerPlan:
             self.gv_noise = torch.zeros_like(self.x)
         if self.keep_regions:
             self.keep = torch.zeros(b * n_cam, h, w, dtype=F32, device=device)         # one value per latent pixel (mask_elems = Cl)
+        if resample is not None or self.stochastic:                                    # one seed per view, for the jumps and the step noise alike
+            self.seeds = torch.zeros(b * n_cam, dtype=torch.int64, device=device)
+        if self.stochastic:
+            self.var = torch.zeros(num_steps, 2, dtype=F32, device=device)
+            self.draw_ctr = torch.zeros(1, dtype=torch.int32, device=device)
         # ---------------- prologue ----------------
         self.cond = ConditioningBuffers(bld, cn, cfg, self.c * b, n_cam, L_box, latent_hw, n_text, dynamic=dynamic_boxes, cfg_halves=self.c)
         if self.dynamic_boxes:
@@ -428,8 +442,12 @@ class SamplerPlan:
             if given_view_mode and not self.keep_regions:
                 gv = dict(gv_mask=self.gv_mask, gv_cond=self.gv_cond.view(-1), gv_noise=self.gv_noise.view(-1), gv_mode=given_view_mode,
                           gv_last_step=num_steps - 1)
-            bld.emit(O.DdimStep(self.x.view(-1), self.eps.view(-1), self.coef, self.step_ctr, x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg,
-                                guidance=guidance_scale, xin_c=Cl, name="cfg+ddim", **gv))
+            if self.stochastic:
+                bld.emit(O.DdimEtaStep(self.x.view(-1), self.eps.view(-1), self.coef, self.var, self.step_ctr, self.draw_ctr, seeds=self.seeds,
+                                       x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, guidance=guidance_scale, xin_c=Cl, name="cfg+ddim_eta", **gv))
+            else:
+                bld.emit(O.DdimStep(self.x.view(-1), self.eps.view(-1), self.coef, self.step_ctr, x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg,
+                                    guidance=guidance_scale, xin_c=Cl, name="cfg+ddim", **gv))
         else:
             gv = {}
             if given_view_mode and not self.keep_regions:
@@ -456,7 +474,6 @@ class SamplerPlan:
         self.jump: Optional[L.Program] = None
         if resample is not None:    # a program of its own, launched between steps: one group (one seed) per view
             self.visit_ctr = torch.zeros(1, dtype=torch.int32, device=device)
-            self.seeds = torch.zeros(b * n_cam, dtype=torch.int64, device=device)
             self.jump_ops = [O.LatentRenoise(self.x.view(-1), self.coef, self.step_ctr, self.visit_ctr, self.seeds, jump=resample,
                                              x_in=self.x_in.view(-1, CIN_PAD), cfg=do_cfg, xin_c=Cl, name="resample.jump")]
         self.health_prog: Optional[L.Program] = None
@@ -544,13 +561,14 @@ class SamplerPlan:
     # ---- per-call inputs ----
     def load_inputs(self, latents: torch.Tensor, camera_param, text, bev_map, boxes, timesteps: torch.Tensor, coef: torch.Tensor,
                     given_mask: Optional[torch.Tensor] = None, given_latents: Optional[torch.Tensor] = None,
-                    keep_mask: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None):
+                    keep_mask: Optional[torch.Tensor] = None, seeds: Optional[torch.Tensor] = None, var: Optional[torch.Tensor] = None):
         """latents (b, n_cam, C, h, w) any float dtype; camera/text/map/boxes already hold the [uncond | cond] halves.
         given_mask (b, n_cam) bool + given_latents (b, n_cam, C, h, w): the known views of a given-view plan.
         keep_mask (b, n_cam, h, w) in [0, 1], a keep_regions plan only (validated by the caller; zero on views that are not given): the
         first sample is m * add_noise(cond, noise, t_0) + (1 - m) * noise, with exact m == 1 / m == 0 taking the term itself.
         seeds (b,) int64, a resample plan only: one seed per scene, replicated over its views (the jump noise is shared across the views
-        of a scene like the initial noise); visit_ctr restarts at zero."""
+        of a scene like the initial noise); visit_ctr restarts at zero.
+        var (num_steps, 2) fp32, a stochastic plan only (DDIMScheduler.variance_table(eta)), with the same seeds: draw_ctr restarts at zero."""
         b, nc = self.b, self.n_cam
         assert latents.shape[:2] == (b, nc)
         xl = latents.to(self.device, F32).reshape(b * nc, *latents.shape[2:]).permute(0, 2, 3, 1).contiguous()
@@ -585,12 +603,19 @@ class SamplerPlan:
         self.temb_cn.t.copy_(t); self.temb_un.t.copy_(t)
         self.coef.copy_(coef.to(self.device, F32))
         self.step_ctr.zero_()
-        if self.resample is not None:
+        if self.resample is not None or self.stochastic:
             assert seeds is not None and tuple(seeds.shape) == (b,) and seeds.dtype == torch.int64, "seeds must be (b,) int64"
             self.seeds.copy_(seeds.to(self.device).repeat_interleave(nc))
-            self.visit_ctr.zero_()
         else:
             assert seeds is None, "this plan was built without resample"
+        if self.resample is not None:
+            self.visit_ctr.zero_()
+        if self.stochastic:
+            assert var is not None and tuple(var.shape) == (self.num_steps, 2), "var must be (num_steps, 2): DDIMScheduler.variance_table(eta)"
+            self.var.copy_(var.to(self.device, F32))
+            self.draw_ctr.zero_()
+        else:
+            assert var is None, "this plan was built without stochastic"
         if self._health is not None:
             self._health.zero_()
         if self.scheduler_kind == "unipc":

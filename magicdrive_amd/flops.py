@@ -82,6 +82,9 @@ def op_bytes(op) -> float:
     if isinstance(op, O.LatentRenoise):
         # 0 MFMA flops; x read and written, the seeds, the x_in copies (the noise is never in memory)
         return 2 * nb(op.x) + nb(op.seeds) + nb(op.x_in)
+    if isinstance(op, O.DdimEtaStep):
+        # 0 MFMA flops; x read and written, eps, the seeds or the caller's noise, the x_in copies (generated noise is never in memory)
+        return 2 * nb(op.x) + nb(op.eps) + (nb(op.noise) if op.noise is not None else nb(op.seeds)) + nb(op.x_in)
     if isinstance(op, O.ImageComposite):
         # 0 MFMA flops; gen and orig read, out (and the matte) written, the keep cells and the has bytes
         return nb(op.gen) + nb(op.orig) + nb(op.keep) + nb(op.out) + nb(op.matte) + nb(op.has)

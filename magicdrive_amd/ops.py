@@ -806,6 +806,63 @@ class LatentRenoise:
 
 
 @dataclass
+class DdimEtaStep:
+    """The DDIM step with eta > 0 (MdxDdimEtaDesc, csrc/noise.hip), in the scheduler op's place: DdimStep's fields and update, plus
+    var fp32 [steps, 2] = (dir, std) per step (DDIMScheduler.variance_table), draw int32 [1] (steps of this op taken so far, read and
+    written like step) and the source of z: seeds int64 / uint64 [groups], one per n / groups consecutive elements (a view) — Philox4x32-10
+    + Box-Muller of (seeds[g], draw, e) in the step's own domain (include/mdx.h has the mapping to the bit) — or noise fp32 [n], the
+    caller's own (it wins; groups is then 1 unless seeds is given too).  x <- c2 x0 + dir e + std z; a row with std == 0 and dir = c3
+    gives DdimStep's bits.  n_rows: rows of coef and var (by default coef's).  The build follows x_in's 16-bit type (dtype_code)."""
+    x: torch.Tensor                      # fp32 [n] latents, updated in place
+    eps: torch.Tensor                    # fp32 [c*n] ([uncond | cond] when cfg)
+    coef: torch.Tensor                   # fp32 [steps, 4]: DdimStep's table, unchanged
+    var: torch.Tensor                    # fp32 [steps, 2]
+    step: torch.Tensor                   # int32 [1], read and written
+    draw: torch.Tensor                   # int32 [1], read and written
+    seeds: Optional[torch.Tensor] = None
+    noise: Optional[torch.Tensor] = None
+    n_rows: int = -1                     # -1: coef.shape[0]
+    x_in: Optional[torch.Tensor] = None
+    cfg: bool = False
+    guidance: float = 1.0
+    xin_c: int = 0
+    name: str = ""
+    gv_mask: Optional[torch.Tensor] = None
+    gv_cond: Optional[torch.Tensor] = None
+    gv_noise: Optional[torch.Tensor] = None
+    gv_mode: int = 0
+    gv_last_step: int = 0
+    opcode = L.OP_DDIM_ETA
+
+    def lower(self):
+        n = self.x.numel()
+        what = f"ddim_eta {self.name}"
+        _chk(self.x.dtype == F32 and self.x.is_contiguous(), f"{what}: x must be fp32, dense")
+        _chk(self.eps.dtype == F32 and self.eps.is_contiguous() and self.eps.numel() == n * (2 if self.cfg else 1), f"{what}: eps must be fp32, dense, {2 if self.cfg else 1} x n")
+        _chk(self.coef.dtype == F32 and self.coef.dim() == 2 and self.coef.is_contiguous() and self.coef.shape[1] == 4 and self.coef.shape[0] >= 1,
+             f"{what}: coef fp32 [steps, 4]")
+        rows = self.coef.shape[0] if self.n_rows < 0 else self.n_rows
+        _chk(isinstance(rows, int) and not isinstance(rows, bool) and 1 <= rows <= self.coef.shape[0], f"{what}: n_rows={self.n_rows!r} must be in [1, {self.coef.shape[0]}]")
+        _chk(self.var.dtype == F32 and self.var.is_contiguous() and tuple(self.var.shape) == (self.coef.shape[0], 2), f"{what}: var fp32 [steps={self.coef.shape[0]}, 2]")
+        _chk(all(t.dtype == torch.int32 and t.numel() == 1 for t in (self.step, self.draw)), f"{what}: step and draw int32 [1]")
+        _chk(self.seeds is not None or self.noise is not None, f"{what}: seeds or noise must be given")
+        groups = 1
+        if self.seeds is not None:
+            _chk(self.seeds.dtype in (torch.int64, torch.uint64) and self.seeds.is_contiguous() and self.seeds.numel() > 0 and n % self.seeds.numel() == 0,
+                 f"{what}: seeds must be int64, dense, with a size dividing n={n}")
+            groups = self.seeds.numel()
+        if self.noise is not None:
+            _chk(self.noise.dtype == F32 and self.noise.is_contiguous() and self.noise.numel() == n, f"{what}: noise must be fp32, dense, of x's size")
+        d = L.MdxDdimEtaDesc()
+        d.x, d.eps, d.coef, d.var, d.step_ptr, d.draw_ptr = _p(self.x), _p(self.eps), _p(self.coef), _p(self.var), _p(self.step), _p(self.draw)
+        d.seeds, d.noise, d.guidance = _p(self.seeds), _p(self.noise), float(self.guidance)
+        _lower_xin(d, what, self.x_in, n, self.cfg, self.xin_c)
+        _lower_given_views(d, what, n, self.gv_mode, self.gv_mask, self.gv_cond, self.gv_noise, self.gv_last_step)
+        d.group_elems, d.n_rows = max(n // groups, 1), rows
+        return self.opcode, d
+
+
+@dataclass
 class ImageComposite:
     """Composite a kept-region edit with the recorded pictures (MdxCompositeDesc, csrc/composite.hip), on the VAE decoder's output.
     gen [V, C, H, W] in [-1, 1]: bf16, fp16 or fp32, a view with unit inner stride (a channel slice or a wider row pitch is taken as it

@@ -10,7 +10,7 @@ Scope notes: CLIP text encoding is outside the built hot path (a
 it; `prompt_embeds=` bypasses it).  The VAE decode runs on the HIP kernels: `from_pretrained` attaches
 `magicdrive_amd.networks.autoencoder_kl.AutoencoderKL` from `<sd15>/vae` exactly where the reference's `from_pretrained` attaches
 diffusers' (misc/test_utils.py:118-126); a caller-supplied torch VAE is still accepted.
-Fused schedulers: DDIM eta=0 (the north-star config) and UniPC (what tools/test.py installs); others raise.
+Fused schedulers: DDIM (eta = 0, the north-star config, and eta > 0 with device-side variance noise) and UniPC (what tools/test.py installs); others raise.
 """
 from __future__ import annotations
 
@@ -374,10 +374,11 @@ class StableDiffusionBEVControlNetPipeline:
         return (cap, "scene", (cap, "scene")) if scene else (cap, True, (cap, "dynamic"))
 
     def _plan_key(self, n_scene, chunk, do_cfg, box_key, h, w, n_steps, guidance_scale, conditioning_scale, n_text, sched_kind, gv_mode, pdt, fork,
-                  health=None, regions=False, resample=None):
+                  health=None, regions=False, resample=None, stochastic=False):
         """Cache key of one scene chunk's SamplerPlan.  `health` enters as a trailing entry only when it is on: with the switch off the key is,
         entry for entry, what it was before the switch existed.  Likewise `regions` (pipe.keep_masks set): a trailing ("regions",), and
-        `resample` (pipe.resample set; the jump length: jump_n_sample only shapes the loop): a trailing ("resample", jump_length)."""
+        `resample` (pipe.resample set; the jump length: jump_n_sample only shapes the loop): a trailing ("resample", jump_length), and
+        `stochastic` (a call with eta > 0; eta's value is data of the plan, not part of its key): a trailing ("eta",)."""
         key = (n_scene, chunk, do_cfg, box_key, h, w, n_steps, float(guidance_scale), float(conditioning_scale), n_text, sched_kind,
                gv_mode, pdt, id(self.unet.packed()), id(self.controlnet.packed()), fork)
         if health is not None:
@@ -386,6 +387,8 @@ class StableDiffusionBEVControlNetPipeline:
             key = key + (("regions",),)
         if resample is not None:
             key = key + (("resample", int(resample)),)
+        if stochastic:
+            key = key + (("eta",),)
         return key
 
     def _checked_resample(self) -> Tuple[int, int]:
@@ -511,8 +514,7 @@ class StableDiffusionBEVControlNetPipeline:
             # the reference forwards these to the UNet's attention processors (:420); the fused attention has no such hooks — refuse,
             # like attention_mask, instead of silently ignoring them
             raise NotImplementedError(f"cross_attention_kwargs={cross_attention_kwargs!r}: the fused attention kernels take no processor kwargs")
-        if eta != 0.0:
-            raise NotImplementedError("the fused samplers are deterministic (DDIM eta = 0, UniPC)")
+        eta = DDIMScheduler.checked_eta(eta)                   # ValueError for a negative or non-finite eta, before anything else of the call
         if self.scene_boxes and bbox_max_length is not None:
             raise ValueError(f"bbox_max_length={bbox_max_length!r} with scene_boxes=True: bbox_max_length asks for the padded slots as tokens every "
                              "scene attends to, scene_boxes for every scene attending to its own boxes only — pass one of the two")
@@ -522,6 +524,13 @@ class StableDiffusionBEVControlNetPipeline:
             sched_kind = "unipc"
         else:
             raise NotImplementedError(f"{type(self.scheduler).__name__}: fused steps exist for magicdrive_amd.schedulers.DDIMScheduler and UniPCMultistepScheduler")
+        # eta > 0 (DDIM only): the stochastic plan — ops.DdimEtaStep in the scheduler op's place, its variance noise made on the device from
+        # one int64 seed per scene (the draw of pipe.resample: AFTER the initial latents, from each scene's own generator in list form; with
+        # both switches on it is ONE draw).  eta's value is data of the plan (SamplerPlan.var): every eta > 0 shares one captured plan.
+        # The last step adds noise too (std about 0.02 eta at SD-1.5's schedule), as diffusers does; the noise is not torch's.
+        stochastic = eta > 0.0
+        if stochastic and sched_kind != "ddim":
+            raise NotImplementedError("the fused UniPC sampler is deterministic: eta > 0 is built for magicdrive_amd.schedulers.DDIMScheduler (eta is DDIM's parameter)")
         if self._device.type != "cuda":
             raise RuntimeError("pipeline.to('cuda') first: the sampler has no CPU path")
         health = getattr(self, "health", None)
@@ -555,7 +564,7 @@ class StableDiffusionBEVControlNetPipeline:
         num_channels_latents = self.unet.config.in_channels
         latents = self.prepare_latents(b, num_channels_latents, height, width, prompt_embeds.dtype, device, generator, latents)
         jump_seeds = None
-        if resample is not None:      # one int64 seed per scene, drawn AFTER the initial latents from the same generator(s), on the host
+        if resample is not None or stochastic:      # one int64 seed per scene, drawn AFTER the initial latents from the same generator(s), on the host
             if isinstance(generator, (list, tuple)):
                 jump_seeds = torch.cat([torch.empty(1, dtype=torch.int64, device=g.device).random_(generator=g).cpu() for g in generator])
             else:
@@ -621,7 +630,8 @@ class StableDiffusionBEVControlNetPipeline:
             # built on the old PackedNet would keep running (and keep alive) the old ones
             # box_bucket: the key carries (capacity, "dynamic") in the place of L_box, scene_boxes (capacity, "scene"); neither / no boxes: today's key
             key = self._plan_key(s1 - s0, ci, do_cfg, box_key, h, w, n_steps, guidance_scale, controlnet_conditioning_scale, text.shape[1], sched_kind,
-                                 gv_mode, pdt, fork, health, regions=keep is not None, resample=None if resample is None else resample[0])
+                                 gv_mode, pdt, fork, health, regions=keep is not None, resample=None if resample is None else resample[0],
+                                 **({"stochastic": True} if stochastic else {}))
             plan = self._plans.get(key)
             if plan is None:
                 with torch.cuda.device(device):
@@ -634,14 +644,15 @@ class StableDiffusionBEVControlNetPipeline:
                                        conditioning_scale=float(controlnet_conditioning_scale), n_text=text.shape[1], scheduler_kind=sched_kind,
                                        given_view_mode=gv_mode, fork=fork, dynamic_boxes=dyn_boxes, **({} if health is None else {"health": health}),
                                        **({} if keep is None else {"keep_regions": True}),
-                                       **({} if resample is None else {"resample": resample[0]}))
+                                       **({} if resample is None else {"resample": resample[0]}), **({"stochastic": True} if stochastic else {}))
                     plan.compile()
                 self._plans.put(key, plan)
             plan.load_inputs(latents[s0:s1], rows(camera_param, s0, s1), rows(text, s0, s1), rows(image, s0, s1),
                              None if boxes is None else {k: rows(v, s0, s1) for k, v in boxes.items()}, timesteps,
                              self.scheduler.coefficient_table(), given_mask=None if gv_mask is None else gv_mask[s0:s1],
                              given_latents=None if gv_lat is None else gv_lat[s0:s1], **({} if keep is None else {"keep_mask": keep[s0:s1]}),
-                             **({} if jump_seeds is None else {"seeds": jump_seeds[s0:s1]}))
+                             **({} if jump_seeds is None else {"seeds": jump_seeds[s0:s1]}),
+                             **({"var": self.scheduler.variance_table(eta)} if stochastic else {}))
             plans.append(plan)
         with torch.cuda.device(device):                       # launches, graph replays and torch copies all target the pipeline's device
             main = torch.cuda.current_stream(device)

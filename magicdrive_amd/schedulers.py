@@ -8,7 +8,8 @@ fp32 coefficient table {sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev)} th
 
 The reference pipeline raises RuntimeError for any scheduler whose step() takes `generator`
 (pipeline_bev_controlnet.py:94-97) — which includes diffusers' DDIM.  Ours has no `generator`
-parameter (eta = 0 is deterministic), so the guard passes unchanged.
+parameter, so the guard passes unchanged: eta = 0 is deterministic, and eta > 0 takes its variance noise from the caller
+(step(..., variance_noise=)) or, in the pipelines, from one seed per scene on the device (mdx_cfg_ddim_eta_step_*; variance_table).
 """
 from __future__ import annotations
 
@@ -157,11 +158,46 @@ class DDIMScheduler:
             self._table_dev = {}
         return self._table
 
-    def step(self, model_output, timestep, sample, eta: float = 0.0, return_dict: bool = True):
+    @staticmethod
+    def checked_eta(eta) -> float:
+        """eta as a float: finite and >= 0, else ValueError (the one check of step() and of the pipelines)."""
+        try:
+            e = float(eta)
+        except (TypeError, ValueError):
+            raise ValueError(f"eta={eta!r} must be a finite number >= 0") from None
+        if isinstance(eta, bool) or not np.isfinite(e) or e < 0.0:
+            raise ValueError(f"eta={eta!r} must be a finite number >= 0")
+        return e
+
+    def variance_table(self, eta: float) -> torch.Tensor:
+        """fp32 [n_steps, 2]: (dir, std) per inference step, the second table of the eta > 0 kernel (mdx_cfg_ddim_eta_step_*), following
+        scheduling_ddim.py:_get_variance and :415-422: variance = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev), std = eta sqrt(variance),
+        dir = sqrt(1 - a_prev - std^2).  Evaluated like coefficient_table(): in double precision from the fp32 alphas, rounded once.
+        eta = 0: std == 0 and dir == coefficient_table()[:, 3], bit for bit.  1 - a_prev - std^2 = (1 - a_prev) (1 - eta^2 (1 - a_t / a_prev)
+        / (1 - a_t)) turns negative only for eta well above 1; it is clamped at zero there (diffusers would produce NaN)."""
+        eta = self.checked_eta(eta)
+        rows = []
+        for t in self.timesteps.tolist():
+            a_t, a_p = self.alpha_pair(int(t))
+            a_t, a_p = float(a_t), float(a_p)
+            variance = (1 - a_p) / (1 - a_t) * (1 - a_t / a_p)
+            std = eta * max(variance, 0.0) ** 0.5
+            rows.append([max(1 - a_p - std * std, 0.0) ** 0.5, std])
+        return torch.tensor(rows, dtype=torch.float32)
+
+    def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, variance_noise=None,
+             return_dict: bool = True):
         """Single DDIM update through the same fused HIP kernel the pipeline uses (for user code that drives
-        the scheduler itself).  CUDA fp32 tensors only — there is no host implementation."""
-        if eta != 0.0:
-            raise NotImplementedError("eta > 0 needs variance noise; the drop-in builds the deterministic sampler")
+        the scheduler itself).  CUDA fp32 tensors only — there is no host implementation.
+        eta > 0 runs mdx_cfg_ddim_eta_step_* and needs variance_noise (a tensor of sample's shape): this signature has no `generator`
+        — a per-call torch generator has no meaning for a batch of multi-view scenes; the pipelines draw one seed per scene and make
+        the noise on the device (pipe(..., eta=)).  use_clipped_model_output is accepted: without clip_sample it changes nothing."""
+        eta = self.checked_eta(eta)
+        if eta > 0.0 and variance_noise is None:
+            raise ValueError("DDIMScheduler.step(eta > 0) needs variance_noise=: this step takes no generator.  The pipelines make the noise "
+                             "on the device from one seed per scene: pipe(..., eta=eta)")
+        if variance_noise is not None and tuple(variance_noise.shape) != tuple(sample.shape):
+            raise ValueError(f"variance_noise has shape {tuple(variance_noise.shape)}, sample {tuple(sample.shape)}")
         if not (model_output.is_cuda and sample.is_cuda):
             raise RuntimeError("DDIMScheduler.step runs on the GPU kernel; pass CUDA tensors")
         from . import ops as O
@@ -197,7 +233,14 @@ class DDIMScheduler:
             step = idx_dev[int(hits[0]):int(hits[0]) + 1]
         x = sample.detach().to(torch.float32).contiguous().clone()
         eps = model_output.detach().to(torch.float32).contiguous()
-        O.run_ops([O.DdimStep(x.view(-1), eps.view(-1), coef, step.clone())])
+        if eta > 0.0:
+            var = self._table_dev.get(("var", eta, dev))
+            if var is None:
+                var = self._table_dev[("var", eta, dev)] = self.variance_table(eta).to(dev)
+            z = variance_noise.detach().to(dev, torch.float32).contiguous()
+            O.run_ops([O.DdimEtaStep(x.view(-1), eps.view(-1), coef, var, step.clone(), torch.zeros(1, dtype=torch.int32, device=dev), noise=z.view(-1))])
+        else:
+            O.run_ops([O.DdimStep(x.view(-1), eps.view(-1), coef, step.clone())])
         prev = x.to(sample.dtype)
         if not return_dict:
             return (prev,)

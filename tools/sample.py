@@ -4,7 +4,7 @@ load a checkpoint in the reference layout, read the training run's hydra overrid
 (demo/readme.md:3-22) through StableDiffusionBEVControlNetPipeline on the MI355X path and save the six views per scene.
 
   python tools/sample.py --ckpt <ckpt dir with unet/ controlnet/ hydra/overrides.yaml> --sd15 <stable-diffusion-v1-5 dir> \
-         --data <folder of *.pth> --out <dir> [key=value overrides as for tools/test.py] [--scheduler unipc|ddim] [--prompt-embeds]
+         --data <folder of *.pth> --out <dir> [key=value overrides as for tools/test.py] [--scheduler unipc|ddim] [--eta X] [--prompt-embeds]
          [--cond-on-view] [--regenerate-boxes [--region-dilate N] [--resample JL,JN] [--composite [--feather N] [--save-matte]]]
 
 --cond-on-view is demo/run_cond_on_view.py:34-120: the pipe class becomes StableDiffusionBEVControlNetGivenViewPipeline, the ground-truth
@@ -26,6 +26,8 @@ the rank that sampled the scene.  Without the flag the output is byte for byte w
 --resample JL,JN (with --regenerate-boxes and --scheduler ddim only) sets pipe.resample = (jump_length, jump_n_sample): RePaint resampling,
 which gives the model time to harmonise the regenerated boxes with what is kept at the price of more UNet evaluations per call
 (INTEGRATION.md §1); index.json then carries "resample": [JL, JN].  Without the flag the output is byte for byte what it was.
+--eta X (with --scheduler ddim only) is runner.pipeline_param.eta=X: stochastic DDIM with variance noise made on the device from one seed
+per scene; index.json then carries "eta": X.  Without the flag the output is byte for byte what it was.
 
 No hydra / omegaconf / mmdet3d: the config tree of the reference is not rebuilt (SURVEY.md §8 out of scope) — only the handful of
 keys the sampling loop reads are resolved, in the reference's order (checkpoint overrides first, command line last, tools/test.py:46-54):
@@ -333,6 +335,8 @@ def main(argv=None):
     ap.add_argument("--region-dilate", type=int, default=1, help="--regenerate-boxes: grow the regenerated region by N latent pixels (default 1)")
     ap.add_argument("--resample", default=None, metavar="JL,JN", help="--regenerate-boxes with --scheduler ddim: RePaint resampling, pipe.resample = (jump_length, "
                     "jump_n_sample), two integers >= 1 (INTEGRATION.md §1); recorded in index.json")
+    ap.add_argument("--eta", type=float, default=None, metavar="X", help="--scheduler ddim: stochastic DDIM, the same as runner.pipeline_param.eta=X (variance noise made "
+                    "on the device from one seed per scene, INTEGRATION.md §1); finite and >= 0; recorded in index.json")
     ap.add_argument("--composite", action="store_true", help="--regenerate-boxes: composite every view with the sample's recorded picture on the device "
                     "(pipe.composite_images, INTEGRATION.md §1): pixels the matte keeps whole are the recorded bytes; index.json gains composite / kept_fraction")
     ap.add_argument("--feather", type=int, default=None, metavar="N", help="--composite: pipe.composite_feather, the matte's erosion and blur radius in image pixels, 0 to 16 (default 4)")
@@ -367,6 +371,12 @@ def main(argv=None):
         if len(parts) != 2 or not all(p_.strip().isdigit() and int(p_) >= 1 for p_ in parts):
             raise SystemExit(f"--resample {a.resample!r}: JL,JN, two integers >= 1")
         resample = (int(parts[0]), int(parts[1]))
+    if a.eta is not None:
+        if a.scheduler != "ddim":
+            raise SystemExit("--eta needs --scheduler ddim: eta is DDIM's parameter, the fused UniPC sampler is deterministic")
+        if not (a.eta == a.eta and 0.0 <= a.eta < float("inf")):
+            raise SystemExit(f"--eta {a.eta!r}: a finite number >= 0")
+        run["eta"] = float(a.eta)
     if a.composite and not a.regenerate_boxes:
         raise SystemExit("--composite puts the recorded pictures back around a kept-region edit: it is valid with --regenerate-boxes only")
     if (a.feather is not None or a.save_matte) and not a.composite:
@@ -454,6 +464,7 @@ def main(argv=None):
         index.sort(key=lambda r_: (r_["scene"], r_["gen"]))
         with open(os.path.join(a.out, "index.json"), "w") as f:
             json.dump(dict(world=world, seed=run["seed"], gather_images=bool(a.gather_images), **({} if resample is None else {"resample": list(resample)}),
+                           **({} if a.eta is None else {"eta": float(a.eta)}),
                            **({} if feather is None else {"composite": {"feather": feather}}),
                            generations=index), f, indent=1)
         print(f"sampled {len(data)} scenes x {run['validation_times'] - (1 if a.cond_on_view else 0)} on {world} rank(s) -> {a.out}")
