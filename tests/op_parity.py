@@ -7,7 +7,10 @@ walk(ops, execute) runs a program op by op.  Before an op it snapshots every ten
 writes; after `execute(op)` it computes the fp64 reference FROM THE SNAPSHOT and holds the op alone to the kernel-level criterion:
 
   values    16-bit outputs: helpers.close() against fp64, unchanged.  fp32 outputs: the bounds the kernel tests apply to the same kernels
-            (tails_data.F32_REL_L2 for GEMM / conv, ABS_BOUND for TimeEmb and the scheduler ops, ops.GroupStats.chain_length for the records).
+            (tails_data.F32_REL_L2 for GEMM / conv, ABS_BOUND for TimeEmb and the scheduler ops, ops.GroupStats.chain_length for the records;
+            LatentBlend, LatentRenoise, DdimEtaStep and ImageComposite: the per-element bounds of tests/test_latent_blend_gpu.py,
+            test_latent_renoise_gpu.py, test_ddim_eta_gpu.py and test_composite_gpu.py, stated next to their references, with the device
+            noise of tests/philox_ref.py; a latent op's 16-bit x_in is also the rounding of the stored x, bit for bit).
   finite    every output element, except where include/mdx.h says NaN (a key count outside [1, Tk]).
   borders   every byte of an output's storage outside the output view keeps its bits (the other half of a concat buffer, the q / k block next
             to a fused V^T, the V^T pad columns past vt_T, the pad channels of x_in).  Scratch (ws, ln_scratch) is exempt; the columns
@@ -21,9 +24,11 @@ import contextlib
 import dataclasses
 import math
 
+import numpy as np
 import torch
 
 import helpers
+import philox_ref as PH
 import tails_data as T
 import values_data as V
 from magicdrive_amd import _lib as L
@@ -70,7 +75,13 @@ FIELDS = {
     O.DdimStep: Fields(_SCHED, ("x", "x_in", "step")),
     O.UniPCStep: Fields(_SCHED, ("x", "x_in", "step", "x_last", "m1", "m2")),
     O.GroupStats: Fields(("X", "row"), ("out",)),
+    O.Sdpa: Fields(("Q", "K", "V", "klen"), ("O",)),
+    O.LatentBlend: Fields(("cond", "noise", "mask", "coef", "step"), ("x", "x_in")),
+    O.LatentRenoise: Fields(("coef", "seeds"), ("x", "x_in", "step", "visit")),
+    O.DdimEtaStep: Fields(_SCHED + ("var", "seeds", "noise"), ("x", "x_in", "step", "draw")),
+    O.ImageComposite: Fields(("gen", "orig", "keep", "has"), ("out", "matte")),
 }
+LATENT_OPS = (O.LatentBlend, O.LatentRenoise, O.DdimEtaStep)      # fp32 x with a per-element bound of its own, x_in its 16-bit rounding
 
 
 def fields_of(op) -> Fields:
@@ -114,14 +125,25 @@ def out_views(op, shadow=None):
         if op.rowstat is not None:
             v["rowstat"] = op.rowstat
         return v
-    if isinstance(op, O.Attn):
+    if isinstance(op, (O.Attn, O.Sdpa)):
         return {"O": op.O}
-    if isinstance(op, (O.DdimStep, O.UniPCStep)):
-        v = {"x": op.x, "step": op.step}
+    if isinstance(op, (O.DdimStep, O.UniPCStep) + LATENT_OPS):
+        v = {"x": op.x}
+        if not isinstance(op, O.LatentBlend):             # the blend reads the counter the scheduler op has advanced
+            v["step"] = op.step
         if op.x_in is not None:
             v["x_in"] = op.x_in if op.x_in.dtype == torch.float32 else op.x_in[:, :op.xin_c]
         if isinstance(op, O.UniPCStep):
             v.update(x_last=op.x_last, m1=op.m1, m2=op.m2)
+        if isinstance(op, O.LatentRenoise):
+            v["visit"] = op.visit
+        if isinstance(op, O.DdimEtaStep):
+            v["draw"] = op.draw
+        return v
+    if isinstance(op, O.ImageComposite):
+        v = {"out": op.out}
+        if op.matte is not None:
+            v["matte"] = op.matte
         return v
     if isinstance(op, O.GroupStats):
         if op.row is not None:
@@ -452,15 +474,213 @@ def ref_group_stats(op):
     return {"out": rec}
 
 
+def ref_sdpa(op):
+    """MdxSdpaDesc: softmax(scale Q K^T + mask) V per head; causal: key j visible to query i iff j <= i; klen: batch b sees its first
+    klen[b] keys, a count outside [1, Tk] gives NaN rows for that batch."""
+    Q, K, Vv = op.Q.to(F64), op.K.to(F64), op.V.to(F64)
+    B, Tq, C = Q.shape
+    Tk, H = K.shape[1], op.heads
+    d = C // H
+    heads = lambda x: x.reshape(x.shape[0], H, d).transpose(0, 1)
+    counts = op.klen.tolist() if op.klen is not None else [Tk] * B
+    out = torch.zeros(B, Tq, C, dtype=F64, device=Q.device)
+    causal = torch.ones(Tq, Tk, dtype=torch.bool, device=Q.device).tril() if op.causal else None
+    for b in range(B):
+        n = counts[b]
+        if n < 1 or n > Tk:
+            out[b] = math.nan
+            continue
+        s = heads(Q[b]) @ heads(K[b, :n]).transpose(1, 2) * op.scale
+        if causal is not None:
+            s = s.masked_fill(~causal[:, :n], -math.inf)
+        out[b] = (torch.softmax(s, -1) @ heads(Vv[b, :n])).transpose(0, 1).reshape(Tq, C)
+    return {"O": out}
+
+
+# The four latent ops below return, next to their outputs, "_bound": {field: per-element absolute bound, fp64} — the bound the op's own
+# kernel test applies to the same kernel — and "_written": the elements of x the contract says are written (their x_in copies must be the
+# 16-bit rounding of the stored x, bit for bit, as every one of those kernel tests asserts).
+NOISE_LIMIT = 1e-5                            # tests/test_latent_renoise_gpu.py: |z_fp32 - z_fp64| of the documented evaluation
+ULP = 2.0 ** -23                              # tests/test_ddim_eta_contract.py: one fp32 operation charged one ulp
+
+
+def _xin_ref(op, xn, written):
+    """x_in after a latent op: the new latents in every CFG half where the op wrote them, the snapshot's value elsewhere."""
+    c = 2 if op.cfg else 1
+    old = op.x_in.to(F64)
+    if op.x_in.dtype == torch.float32:
+        return torch.where(written.repeat(c), xn.repeat(c), old.reshape(-1)).reshape(op.x_in.shape)
+    new = xn.reshape(-1, op.xin_c).repeat(c, 1)
+    return torch.where(written.reshape(-1, op.xin_c).repeat(c, 1), new, old[:, :op.xin_c])
+
+
+def _group_noise(seeds, counter, n, fn, device):
+    """fp64 [n]: fn(seed, counter, n / groups) of every group, in order (tests/philox_ref.py)."""
+    ge = n // seeds.numel()
+    return torch.from_numpy(np.concatenate([fn(int(s), counter, ge) for s in seeds.tolist()])).to(device)
+
+
+def ref_latent_blend(op):
+    """MdxBlendDesc.  Bound (tests/test_latent_blend_gpu.py): 4 * 2^-24 * (|a cond| + |sg noise| + |x|) where something is written; an
+    m == 0 element keeps its bits."""
+    n = op.x.numel()
+    x = op.x.to(F64).reshape(-1)
+    s = _int(op.step) - 1
+    ld = op.coef.shape[1]
+    ca, cs = (op.col_a, op.col_s) if min(op.col_a, op.col_s) >= 0 else O.LatentBlend.COLUMNS[ld]
+    if s < 0 or s >= op.last_step:
+        xn, written, bound = x, torch.zeros(n, dtype=torch.bool, device=x.device), torch.zeros_like(x)
+    else:
+        a, sg = op.coef[s, ca].to(F64), op.coef[s, cs].to(F64)
+        m = op.mask.to(F64).reshape(-1).repeat_interleave(n // op.mask.numel())
+        ac, sn = a * op.cond.to(F64).reshape(-1), sg * op.noise.to(F64).reshape(-1)
+        t = ac + sn
+        xn = torch.where(m == 0, x, torch.where(m == 1, t, x + m * (t - x)))
+        written = m != 0
+        bound = torch.where(written, 4 * U24 * (ac.abs() + sn.abs() + x.abs()), torch.zeros_like(x))
+    out = {"x": xn.reshape(op.x.shape), "_bound": {"x": bound.reshape(op.x.shape)}, "_written": written}
+    if op.x_in is not None:
+        out["x_in"] = _xin_ref(op, xn, written)
+    return out
+
+
+def ref_latent_renoise(op):
+    """MdxRenoiseDesc, with the contract's fp32 r and sg (a correctly rounded division, 1 - r r with one rounding, a correctly rounded
+    square root) as tests/test_latent_renoise_gpu.py takes them.  Bound (the same test): 1e-5 sg + 4 * 2^-24 |ref|."""
+    n = op.x.numel()
+    x = op.x.to(F64).reshape(-1)
+    c, v = _int(op.step), _int(op.visit)
+    ld, rows = op.coef.shape[1], op.coef.shape[0]
+    ct, cp = (op.col_t, op.col_p) if min(op.col_t, op.col_p) >= 0 else O.LatentRenoise.COLUMNS[ld]
+    keep = {"step": op.step.to(F64), "visit": op.visit.to(F64)}
+    if op.jump < 1 or c < 1 or c > rows or c - op.jump < 0:      # x is filled with NaN, x_in and both counters are left alone
+        out = {"x": torch.full(op.x.shape, math.nan, dtype=F64, device=x.device), "_bound": {}, "_written": torch.zeros(n, dtype=torch.bool, device=x.device), **keep}
+        if op.x_in is not None:
+            out["x_in"] = _xin_ref(op, x, out["_written"])
+        return out
+    r32 = op.coef[c - op.jump, ct].float() / op.coef[c - 1, cp].float()
+    r = r32.to(F64)
+    sg = (1.0 - r * r).float().clamp_min(0).sqrt().to(F64)
+    z = _group_noise(op.seeds, v, n, PH.noise_ref, x.device)
+    xn = r * x + sg * z
+    written = torch.ones(n, dtype=torch.bool, device=x.device)
+    out = {"x": xn.reshape(op.x.shape), "step": op.step.to(F64) - op.jump, "visit": op.visit.to(F64) + 1,
+           "_bound": {"x": (NOISE_LIMIT * sg + 4 * U24 * xn.abs()).reshape(op.x.shape)}, "_written": written}
+    if op.x_in is not None:
+        out["x_in"] = _xin_ref(op, xn, written)
+    return out
+
+
+def ref_ddim_eta(op):
+    """MdxDdimEtaDesc.  Bound: the scheduler-level one of tests/test_ddim_eta_gpu.py for the kernel's own roundings, 9 * ULP * S with
+    S = c2 (|x| + c1 |e|) / c0 + dir |e| + std |z| and ULP = 2^-23, plus the 1e-5 std of a generated z (tests/test_latent_renoise_gpu.py);
+    the table terms of that test are absent because var IS this op's table.  Under CFG |e| stands for |eps_u| + g |eps_c - eps_u|, the sum of
+    the magnitudes the three roundings of the guidance combine act on (it bounds |e|, and 3 * 2^-24 of it bounds their error: within the
+    18 * 2^-24 S of the nine operations).  A gv_mode 1 element is two products and a sum: the kernel test's 2 * 2^-24 (|c2 cond| + |c3 noise| + |t|)."""
+    n = op.x.numel()
+    x = op.x.to(F64).reshape(-1)
+    s, v = _int(op.step), _int(op.draw)
+    rows = op.coef.shape[0] if op.n_rows < 0 else op.n_rows
+    keep = {"step": op.step.to(F64), "draw": op.draw.to(F64)}
+    if s < 0 or s >= rows:
+        out = {"x": torch.full(op.x.shape, math.nan, dtype=F64, device=x.device), "_bound": {}, "_written": torch.zeros(n, dtype=torch.bool, device=x.device), **keep}
+        if op.x_in is not None:
+            out["x_in"] = _xin_ref(op, x, out["_written"])
+        return out
+    c = op.coef[s].to(F64)
+    dirv, std = (torch.full_like(x, float(t)) for t in op.var[s].to(F64))
+    eps = op.eps.to(F64).reshape(-1)
+    if op.cfg:
+        g = float(np.float32(op.guidance))
+        e = eps[:n] + g * (eps[n:] - eps[:n])
+        emag = eps[:n].abs() + g * (eps[n:] - eps[:n]).abs()
+    else:
+        e, emag = eps, eps.abs()
+    given = torch.zeros(n, dtype=torch.bool, device=x.device)
+    if op.gv_mode:
+        given = op.gv_mask.bool().repeat_interleave(n // op.gv_mask.numel())
+        if op.gv_mode == 2:
+            gn = op.gv_noise.to(F64).reshape(-1)
+            e, emag = torch.where(given, gn, e), torch.where(given, gn.abs(), emag)
+            dirv, std = torch.where(given, c[3], dirv), torch.where(given, torch.zeros_like(std), std)
+    if op.noise is not None:
+        z, zerr = op.noise.to(F64).reshape(-1), 0.0
+    else:
+        z, zerr = _group_noise(op.seeds, v, n, PH.eta_noise_ref, x.device), NOISE_LIMIT
+    x0 = (x - c[1] * e) / c[0]
+    xn = c[2] * x0 + dirv * e + std * z
+    S = c[2] * (x.abs() + c[1] * emag) / c[0] + dirv * emag + std * z.abs()
+    bound = 9 * ULP * S + zerr * std
+    if op.gv_mode == 1 and s < op.gv_last_step:
+        cc, nn = c[2] * op.gv_cond.to(F64).reshape(-1), c[3] * op.gv_noise.to(F64).reshape(-1)
+        xn = torch.where(given, cc + nn, xn)
+        bound = torch.where(given, 2 * U24 * (cc.abs() + nn.abs() + (cc + nn).abs()), bound)
+    written = torch.ones(n, dtype=torch.bool, device=x.device)
+    out = {"x": xn.reshape(op.x.shape), "step": op.step.to(F64) + 1, "draw": op.draw.to(F64) + 1, "_bound": {"x": bound.reshape(op.x.shape)}, "_written": written}
+    if op.x_in is not None:
+        out["x_in"] = _xin_ref(op, xn, written)
+    return out
+
+
+def _matte64(keep, f, r):
+    """MdxCompositeDesc's matte in fp64: a = nearest upsample of keep, e = min of a over the (2r+1)^2 window, w = the mean of e over the
+    (2r+1)^2 window, every coordinate clamped to the image."""
+    a = keep.to(F64).repeat_interleave(f, dim=-2).repeat_interleave(f, dim=-1)
+    if r == 0:
+        return a
+    H, W = a.shape[-2:]
+    iy, ix = torch.arange(H, device=a.device), torch.arange(W, device=a.device)
+    win = range(-r, r + 1)
+    e = torch.stack([a[..., (iy + k).clamp(0, H - 1), :] for k in win]).amin(0)
+    e = torch.stack([e[..., (ix + k).clamp(0, W - 1)] for k in win]).amin(0)
+    s = torch.stack([e[..., (iy + k).clamp(0, H - 1), :] for k in win]).sum(0)
+    s = torch.stack([s[..., (ix + k).clamp(0, W - 1)] for k in win]).sum(0)
+    return s / float((2 * r + 1) ** 2)
+
+
+def ref_image_composite(op):
+    """MdxCompositeDesc.  g is the contract's own value, bit for bit: fmaf(gen, 0.5, 0.5) is ONE fp32 rounding of the exact sum, then the
+    rounding to gen's 16-bit type, then the clamp.  Bounds (tests/test_composite_gpu.py): the matte within 2^-24 for masks on the 1/64 grid
+    (every window sum exact), within (2 (2r+1) + 2) * 2^-24 for any other mask; out bit-equal to g where w == 0 and to orig where w == 1,
+    within 4 * 2^-24 between — plus, off the grid only, the matte's own bound times |orig - g|, which is how far that error can move the
+    mix.  has[v] == 0: out = g, matte = 0."""
+    gen = op.gen
+    r = int(op.feather)
+    V, Cc, H, W = gen.shape
+    f = H // op.keep.shape[1]
+    g32 = (gen.to(F64) * 0.5 + 0.5).float()
+    if gen.dtype != torch.float32:
+        g32 = g32.to(gen.dtype).float()
+    g = g32.clamp(0, 1).to(F64).permute(0, 2, 3, 1)
+    w = _matte64(op.keep, f, r)
+    orig = op.orig.to(F64)
+    on_grid = bool((op.keep.to(F64) * 64 == (op.keep.to(F64) * 64).round()).all())
+    mb = U24 if on_grid else (2 * (2 * r + 1) + 2) * U24
+    if op.has is not None:
+        absent = (op.has == 0).view(V, 1, 1)
+        w = torch.where(absent, torch.zeros_like(w), w)
+        orig = torch.where(absent[..., None], g, orig)        # the orig and keep rows of such a view are not read
+    w4 = w[..., None]
+    zero, one = w4 == 0, w4 == 1
+    ref = torch.where(zero, g, torch.where(one, orig, g + w4 * (orig - g)))
+    ob = torch.where(zero | one, torch.zeros_like(ref), 4 * U24 + (0.0 if on_grid else mb) * (orig - g).abs())
+    exact = (w == 0) | (w == 1)
+    out = {"out": ref, "_bound": {"out": ob, "matte": torch.where(exact, torch.zeros_like(w), torch.full_like(w, mb)) if on_grid else torch.full_like(w, mb)}}
+    if op.matte is not None:
+        out["matte"] = w
+    return out
+
+
 REFERENCE = {O.Gemm: ref_gemm, O.Conv: ref_conv, O.Attn: ref_attn, O.GroupNorm: ref_groupnorm, O.GroupNormResident: ref_groupnorm,
              O.LayerNorm: ref_layernorm, O.Softmax: ref_softmax, O.Ew: ref_ew, O.Upsample: ref_upsample, O.Layout: ref_layout,
              O.Fourier: ref_fourier, O.Gather: ref_gather, O.TimeEmb: ref_timeemb, O.DdimStep: ref_ddim, O.UniPCStep: ref_unipc,
-             O.GroupStats: ref_group_stats}
+             O.GroupStats: ref_group_stats, O.Sdpa: ref_sdpa, O.LatentBlend: ref_latent_blend, O.LatentRenoise: ref_latent_renoise,
+             O.DdimEtaStep: ref_ddim_eta, O.ImageComposite: ref_image_composite}
 
 
 def reference(op):
     """{output field: fp64 tensor of the shape of out_views(op)[field]} — every output field except Gemm.rowstat, which include/mdx.h
-    defines on the STORED C (rowstat_reference)."""
+    defines on the STORED C (rowstat_reference).  Keys that start with "_" are not outputs (the latent ops' bounds)."""
     fields_of(op)
     with torch.no_grad():
         return REFERENCE[type(op)](op)
@@ -591,8 +811,21 @@ class Record:
     failures: list = dataclasses.field(default_factory=list)
 
 
-def _judge_values(op, shadow, field, out, ref, rec, plan, fail):
-    """Values + finite for one output field."""
+def _judge_xin_bits(op, aux, fail):
+    """A latent op's 16-bit x_in: every CFG half of a written element is the rounding of the STORED x, bit for bit."""
+    if op.x_in is None or op.x_in.dtype == torch.float32 or not bool(aux["_written"].any()):
+        return
+    wr = aux["_written"].reshape(-1, op.xin_c)
+    want = op.x.reshape(-1, op.xin_c).to(op.x_in.dtype)
+    halves = op.x_in[:, :op.xin_c].reshape(2 if op.cfg else 1, -1, op.xin_c)
+    for hf in range(halves.shape[0]):
+        if not torch.equal(_bits(halves[hf][wr]), _bits(want[wr])):
+            fail("values", f"x_in half {hf} is not the 16-bit rounding of the stored x")
+
+
+def _judge_values(op, shadow, field, out, ref, rec, plan, fail, aux=None):
+    """Values + finite for one output field.  aux: everything reference() returned (the latent ops' bounds)."""
+    aux = aux or {}
     if out.numel() == 0:
         if ref.numel() != 0:
             fail("values", f"{field}: nothing to write but the reference has {ref.numel()} elements")
@@ -635,7 +868,20 @@ def _judge_values(op, shadow, field, out, ref, rec, plan, fail):
         return
     # fp32 outputs
     o64 = out.to(F64)
-    if isinstance(op, (O.Gemm, O.Conv)):
+    if isinstance(op, LATENT_OPS + (O.ImageComposite,)):          # a per-element bound from the op's own kernel test (see the references)
+        b = aux.get("_bound", {})
+        if field == "x_in":                   # an fp32 x_in holds x itself, once per CFG half
+            bx = b.get("x")
+            bound = bx.reshape(-1).repeat(2 if op.cfg else 1).reshape(out.shape) if bx is not None else torch.zeros_like(ref)
+        else:
+            bound = b[field]
+        err = (o64 - ref).abs()
+        w = float((err / bound.clamp_min(1e-300)).max())          # a bound of zero (an element the contract leaves alone or copies) asks for the bits
+        rec.rel_l2, rec.worst = max(rec.rel_l2, rel_l2_64(o64, ref)), max(rec.worst, min(w, 1e30))
+        if not w <= 1.0:
+            at = int((err / bound.clamp_min(1e-300)).reshape(-1).argmax())
+            fail("values", f"{field}: |err| / bound = {w:.3e} at element {at} (|err| {float(err.reshape(-1)[at]):.3e}, bound {float(bound.reshape(-1)[at]):.3e})")
+    elif isinstance(op, (O.Gemm, O.Conv)):
         rel = rel_l2_64(o64, ref)
         rec.rel_l2, rec.worst = max(rec.rel_l2, rel), max(rec.worst, rel / T.F32_REL_L2)
         if not rel < T.F32_REL_L2:
@@ -753,7 +999,9 @@ def walk(ops, execute, compare=all, kernel=None, plan="", stop=True):
                 else:
                     if k not in ref:
                         raise NotImplementedError(f"op_parity: {type(op).__name__}.{k} has no reference")
-                    _judge_values(op, shadow, k, v, ref[k], rec, plan, fail)
+                    _judge_values(op, shadow, k, v, ref[k], rec, plan, fail, aux=ref)
+            if isinstance(op, LATENT_OPS):
+                _judge_xin_bits(op, ref, fail)
             for key, (v, before, mask) in stor.items():
                 moved = (_storage_bytes(v) != before) & ~mask
                 if bool(moved.any()):

@@ -7,9 +7,11 @@ rounding and buffer reuse behave as on the device.
 """
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
+import philox_ref as PH
 from magicdrive_amd import _lib as L
 from magicdrive_amd import ops as O
 
@@ -241,6 +243,84 @@ def run_unipc(op: O.UniPCStep):
     op.step += 1
 
 
+def _refresh_written(op, xn, wr):
+    """_refresh_x_in for the elements `wr` (bool [n]) only: an element an op leaves alone keeps its x_in copies too."""
+    if op.x_in is None:
+        return
+    n = xn.numel()
+    halves = 2 if op.cfg else 1
+    if op.x_in.dtype == torch.float32:
+        flat = op.x_in.view(halves, n)
+        for hf in range(halves):
+            flat[hf][wr] = xn[wr]
+    else:
+        npx = n // op.xin_c
+        v = xn.view(npx, op.xin_c).to(op.x_in.dtype)
+        w = wr.view(npx, op.xin_c)
+        for hf in range(halves):
+            dst = op.x_in[hf * npx:(hf + 1) * npx, :op.xin_c]
+            dst[w] = v[w]
+
+
+def _device_noise(seeds, counter, n, fn):
+    """fp32 [n]: the device's z of every group (one seed per n / groups consecutive elements), tests/philox_ref.py rounded to fp32."""
+    ge = n // seeds.numel()
+    return torch.from_numpy(np.concatenate([fn(int(s), counter, ge) for s in seeds.tolist()])).float()
+
+
+def run_latent_blend(op: O.LatentBlend):
+    """MdxBlendDesc: behind the scheduler op; s = step - 1 outside [0, last_step) writes nothing."""
+    s = int(op.step.item()) - 1
+    if s < 0 or s >= op.last_step:
+        return
+    n = op.x.numel()
+    ca, cs = (op.col_a, op.col_s) if op.col_a >= 0 and op.col_s >= 0 else op.COLUMNS[op.coef.shape[1]]
+    m = op.mask.reshape(-1).repeat_interleave(n // op.mask.numel())
+    t = op.coef[s, ca] * op.cond + op.coef[s, cs] * op.noise
+    xn = torch.where(m == 1, t, torch.addcmul(op.x, m, t - op.x))
+    wr = m != 0
+    op.x[wr] = xn[wr]
+    _refresh_written(op, op.x, wr)
+
+
+def run_latent_renoise(op: O.LatentRenoise):
+    """MdxRenoiseDesc: x <- r x + sg z(seeds, visit), step <- step - jump, visit <- visit + 1; out of range: x is NaN, nothing else moves."""
+    c, v = int(op.step.item()), int(op.visit.item())
+    if op.jump < 1 or c < 1 or c > op.coef.shape[0] or c - op.jump < 0:
+        op.x.fill_(math.nan)
+        return
+    ct, cp = (op.col_t, op.col_p) if op.col_t >= 0 and op.col_p >= 0 else op.COLUMNS[op.coef.shape[1]]
+    r = op.coef[c - op.jump, ct] / op.coef[c - 1, cp]
+    sg = torch.sqrt(torch.clamp(1.0 - r * r, min=0.0))
+    op.x.copy_(r * op.x + sg * _device_noise(op.seeds, v, op.x.numel(), PH.noise_ref))
+    _refresh_x_in(op, op.x)
+    op.step -= op.jump
+    op.visit += 1
+
+
+def run_ddim_eta(op: O.DdimEtaStep):
+    """MdxDdimEtaDesc: DdimStep's update with (dir, std) = var[step] and z = noise, or the device's z of (seeds, draw)."""
+    n = op.x.numel()
+    s, v = int(op.step.item()), int(op.draw.item())
+    rows = op.coef.shape[0] if op.n_rows < 0 else op.n_rows
+    if s < 0 or s >= rows:
+        op.x.fill_(math.nan)
+        return
+    c = op.coef[s]
+    e, given = _guided_eps(op, n)
+    d, sd = op.var[s, 0].expand(n), op.var[s, 1].expand(n)
+    if op.gv_mode == 2:                       # a given element stays on its own add_noise trajectory: dir = c3, no noise
+        d, sd = torch.where(given, c[3], d), torch.where(given, torch.zeros(()), sd)
+    z = op.noise if op.noise is not None else _device_noise(op.seeds, v, n, PH.eta_noise_ref)
+    x0 = (op.x - c[1] * e) / c[0]
+    det = c[2] * x0 + d * e
+    xn = _renoise_given(op, given, c[2], c[3], torch.where(sd != 0, det + sd * z, det))
+    op.x.copy_(xn)
+    _refresh_x_in(op, xn)
+    op.step += 1
+    op.draw += 1
+
+
 def run_softmax(op: O.Softmax):
     y = torch.softmax(op.X[:, :op.T].float() * op.scale, dim=-1)
     op.Y.zero_()
@@ -263,7 +343,8 @@ def run_group_stats(op: O.GroupStats):
 
 DISPATCH = {O.Gemm: run_gemm, O.GroupStats: run_group_stats, O.Conv: run_conv, O.Attn: run_attn, O.GroupNorm: run_groupnorm, O.LayerNorm: run_layernorm,
             O.Ew: run_ew, O.Upsample: run_upsample, O.Layout: run_layout, O.Fourier: run_fourier, O.Gather: run_gather,
-            O.TimeEmb: run_timeemb, O.DdimStep: run_ddim, O.UniPCStep: run_unipc, O.Softmax: run_softmax}
+            O.TimeEmb: run_timeemb, O.DdimStep: run_ddim, O.UniPCStep: run_unipc, O.Softmax: run_softmax, O.GroupNormResident: run_groupnorm,
+            O.LatentBlend: run_latent_blend, O.LatentRenoise: run_latent_renoise, O.DdimEtaStep: run_ddim_eta}
 
 
 def run(ops, lower_check: bool = True):

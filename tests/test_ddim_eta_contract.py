@@ -21,33 +21,13 @@ import pytest
 import torch
 
 from magicdrive_amd import _lib as L
-from test_latent_renoise_contract import noise_words, philox4x32_10, shared_blocks
+from philox_ref import eta_noise_ref, eta_noise_words, noise_words, shared_blocks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 no_device = pytest.mark.skipif(torch.cuda.is_available(), reason="fake device pointers: must not run where a launch could succeed")
 
 
-# ---- the noise reference ---------------------------------------------------------------------------------------------------------
-def eta_noise_words(seed, draw, count, first_block=0):
-    """The uint32 words [ceil(count / 4), 4] of one group: counter (lo32(k), hi32(k), draw, 1), key (lo32(seed), hi32(seed))."""
-    k = np.arange(first_block, first_block + (count + 3) // 4, dtype=np.uint64)
-    ctr = np.stack([k & 0xFFFFFFFF, k >> 32, np.full_like(k, int(draw) & 0xFFFFFFFF), np.ones_like(k)], -1)
-    s = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return philox4x32_10(ctr, np.broadcast_to(np.array([s & 0xFFFFFFFF, s >> 32], dtype=np.uint64), (len(k), 2)))
-
-
-def eta_noise_ref(seed, draw, count, first_block=0):
-    """float64 z of `count` consecutive elements of one group by the mapping of include/mdx.h (renoise's, counter word 3 = 1)."""
-    w = eta_noise_words(seed, draw, count, first_block)
-    u1 = lambda x: ((x >> 8).astype(np.float64) + 1.0) * 2.0 ** -24
-    u2 = lambda x: (x >> 8).astype(np.float64) * 2.0 ** -24
-    z = np.empty((len(w), 4))
-    for a in (0, 2):
-        rad = np.sqrt(-2.0 * np.log(u1(w[:, a])))
-        z[:, a], z[:, a + 1] = rad * np.cos(2 * np.pi * u2(w[:, a + 1])), rad * np.sin(2 * np.pi * u2(w[:, a + 1]))
-    return z.reshape(-1)[:count]
-
-
+# ---- the noise reference (tests/philox_ref.py holds the one copy) ----------------------------------------------------------------
 def test_step_noise_is_a_standard_normal_in_a_domain_of_its_own():
     z = eta_noise_ref(seed=0x1234_5678_9ABC_DEF0, draw=3, count=1 << 18)
     n = z.size

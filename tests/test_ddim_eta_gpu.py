@@ -39,8 +39,8 @@ from magicdrive_amd import _lib as L  # noqa: E402
 from magicdrive_amd import ops as O  # noqa: E402
 from magicdrive_amd import schedulers  # noqa: E402
 from magicdrive_amd.networks import spec  # noqa: E402
-from test_ddim_eta_contract import ULP, _golden, eta_noise_ref, eta_noise_words, table_bounds  # noqa: E402
-from test_latent_renoise_contract import noise_ref, noise_words, shared_blocks  # noqa: E402
+from philox_ref import eta_noise_ref, eta_noise_words, noise_ref, noise_words, shared_blocks  # noqa: E402
+from test_ddim_eta_contract import ULP, _golden, table_bounds  # noqa: E402
 
 U = 2.0 ** -24
 NAN = float("nan")

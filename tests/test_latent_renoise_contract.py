@@ -20,50 +20,13 @@ import pytest
 import torch
 
 from magicdrive_amd import _lib as L
+from philox_ref import noise_ref, noise_words, philox4x32_10, shared_blocks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 no_device = pytest.mark.skipif(torch.cuda.is_available(), reason="fake device pointers: must not run where a launch could succeed")
 
 
-# ---- the noise reference ---------------------------------------------------------------------------------------------------------
-def philox4x32_10(ctr, key):
-    """Philox4x32-10 on uint32 arrays: ctr [..., 4], key [..., 2] -> [..., 4]."""
-    c = [np.asarray(ctr)[..., i].astype(np.uint64) for i in range(4)]
-    k = [np.asarray(key)[..., i].astype(np.uint64) for i in range(2)]
-    M = 0xFFFFFFFF
-    for _ in range(10):
-        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
-        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & M, (p0 >> 32) ^ c[3] ^ k[1], p0 & M]
-        k = [(k[0] + 0x9E3779B9) & M, (k[1] + 0xBB67AE85) & M]
-    return np.stack(c, -1).astype(np.uint32)
-
-
-def noise_words(seed, visit, count, first_block=0):
-    """The uint32 words [ceil(count / 4), 4] of one group from block first_block on: counter (lo32(k), hi32(k), visit, 0), key (lo32(seed), hi32(seed))."""
-    k = np.arange(first_block, first_block + (count + 3) // 4, dtype=np.uint64)
-    ctr = np.stack([k & 0xFFFFFFFF, k >> 32, np.full_like(k, int(visit) & 0xFFFFFFFF), np.zeros_like(k)], -1)
-    s = int(seed) & 0xFFFFFFFFFFFFFFFF
-    return philox4x32_10(ctr, np.broadcast_to(np.array([s & 0xFFFFFFFF, s >> 32], dtype=np.uint64), (len(k), 2)))
-
-
-def noise_ref(seed, visit, count, first_block=0):
-    """float64 z of `count` consecutive elements of one group, starting at relative index 4 * first_block, by the mapping of include/mdx.h."""
-    w = noise_words(seed, visit, count, first_block)
-    u1 = lambda x: ((x >> 8).astype(np.float64) + 1.0) * 2.0 ** -24
-    u2 = lambda x: (x >> 8).astype(np.float64) * 2.0 ** -24
-    z = np.empty((len(w), 4))
-    for a in (0, 2):
-        rad = np.sqrt(-2.0 * np.log(u1(w[:, a])))
-        z[:, a], z[:, a + 1] = rad * np.cos(2 * np.pi * u2(w[:, a + 1])), rad * np.sin(2 * np.pi * u2(w[:, a + 1]))
-    return z.reshape(-1)[:count]
-
-
-def shared_blocks(wa, wb):
-    """How many 4-word blocks two word tables have in common."""
-    rows = lambda w: set(map(bytes, np.ascontiguousarray(w)))
-    return len(rows(wa) & rows(wb))
-
-
+# ---- the noise reference (tests/philox_ref.py holds the one copy) ----------------------------------------------------------------
 def test_philox_known_answers():
     h = lambda s: np.array([int(x, 16) for x in s.split()], dtype=np.uint32)
     for ctr, key, want in (("0 0 0 0", "0 0", "6627e8d5 e169c58d bc57ac4c 9b00dbd8"),

@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 
 from magicdrive_amd import _lib as L  # noqa: E402
 from magicdrive_amd import ops as O  # noqa: E402
-from test_latent_renoise_contract import noise_ref, noise_words, shared_blocks  # noqa: E402
+from philox_ref import noise_ref, noise_words, shared_blocks  # noqa: E402
 
 U = 2.0 ** -24
 NAN = float("nan")

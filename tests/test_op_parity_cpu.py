@@ -7,12 +7,14 @@ counts, absent cross-view slots, the short causal attention, the gather with an 
 import dataclasses
 import math
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import op_parity as P
 import plan_interp
+from call_state import interp           # the interpreter, one op (an attention with key counts: batch by batch over its first n keys)
 from helpers import cfg_inputs, given_view_inputs, scene, state_dicts
 from magicdrive_amd import _lib as L, denoiser as DN, ops as O, packing, schedulers
 from magicdrive_amd.engine import PackedNet
@@ -22,20 +24,6 @@ from oracle import denoiser as D
 CPU = torch.device("cpu")
 BF = torch.bfloat16
 F64 = torch.float64
-
-
-def interp(op):
-    """The interpreter, one op.  It knows nothing of key counts: an attention that carries them is interpreted batch by batch over its first
-    n keys (as tests/test_box_bucket.py does for tk_dev)."""
-    if isinstance(op, O.Attn) and (op.tk_dev is not None or op.tk_rows is not None):
-        B = op.Q.shape[0]
-        counts = [int(op.tk_dev.item())] * B if op.tk_dev is not None else op.tk_rows.tolist()
-        for b, n in enumerate(counts):
-            assert 1 <= n <= op.Tk
-            plan_interp.run([dataclasses.replace(op, Q=op.Q[b:b + 1], K=op.K[b:b + 1, :n], Vt=op.Vt[b:b + 1], O=op.O[b:b + 1], Tk=n, tk_dev=None, tk_rows=None)],
-                            lower_check=False)
-        return
-    plan_interp.run([op], lower_check=False)
 
 
 @pytest.fixture(scope="module")
@@ -216,6 +204,161 @@ def test_every_seeded_fault_fails_at_its_op_and_nowhere_else(tiny):
     with pytest.raises(P.OpParityError) as e:
         P.walk(ops[sp2_first:sp2_first + 1], faulty, plan="tiny")
     assert e.value.op_name == ops[sp2_first].name
+
+
+# ---- the five op classes added since: keep regions, resampling, stochastic DDIM, sdpa, composite --------------------------------------------
+def test_no_op_class_is_without_fields_reference_or_interpreter():
+    """Every op record of magicdrive_amd/ops.py has its FIELDS entry (naming every tensor field the class declares) and its fp64 reference;
+    every one that can occur in a SamplerPlan has its interpreter case.  The next new op cannot be forgotten silently."""
+    classes = [c for c in vars(O).values() if isinstance(c, type) and dataclasses.is_dataclass(c) and hasattr(c, "opcode")]
+    assert len(classes) >= 21 and {O.Sdpa, O.LatentBlend, O.LatentRenoise, O.DdimEtaStep, O.ImageComposite} <= set(classes)
+    for c in classes:
+        assert c in P.FIELDS and c in P.REFERENCE, f"op_parity has no FIELDS / REFERENCE entry for {c.__name__}"
+        f = P.FIELDS[c]
+        known = set(f.inputs) | set(f.outputs) | set(f.scratch)
+        tensors = {fl.name for fl in dataclasses.fields(c) if "Tensor" in str(fl.type)}
+        assert tensors <= known, f"{c.__name__}: tensor fields {sorted(tensors - known)} are in no Fields entry"
+    outside_a_sampler_plan = {O.Sdpa, O.ImageComposite}      # ops.sdpa / the text encoder's own plan; the picture stage behind the VAE
+    for c in set(classes) - outside_a_sampler_plan:
+        assert c in plan_interp.DISPATCH, f"plan_interp has no case for {c.__name__}"
+
+
+def everything_on(tiny):
+    """Stochastic DDIM + keep regions + resample + health trace, one scene, 2 steps: DdimEtaStep, LatentBlend, GroupStats, one jump program."""
+    import call_state as CS
+    cfg, usd, csd, un, cn = tiny
+    nets = (cfg, csd, un, cn)
+    sp = CS.build_plan(nets, "eta_regions_resample_trace", CPU)
+    args, kw = CS.inputs(nets, "eta_regions_resample_trace", "B")
+    sp.load_inputs(*args, **kw)
+    return sp, CS.actions("eta_regions_resample_trace")
+
+
+def f_jump_stream(op, pre):                 # DdimEtaStep: the noise of the jump's domain (counter word 3 = 0) for the step's
+    import philox_ref as PH
+    n, s, v = op.x.numel(), int(op.step.item()) - 1, int(op.draw.item()) - 1
+    z = lambda fn: torch.from_numpy(np.concatenate([fn(int(sd), v, n // op.seeds.numel()) for sd in op.seeds.tolist()])).float()
+    op.x.add_(op.var[s, 1] * (z(PH.noise_ref) - z(PH.eta_noise_ref)))
+    plan_interp._refresh_x_in(op, op.x)
+
+
+def f_alpha_sigma_swapped(op, pre):         # LatentBlend: the two coefficient columns taken for each other
+    op.x.copy_(pre["x"]); op.x_in.copy_(pre["x_in"])
+    plan_interp.run([dataclasses.replace(op, col_a=3, col_s=2)], lower_check=False)
+
+
+def f_visit_not_advanced(op, pre):          # LatentRenoise: the jump counter stays: the next jump would repeat this one's noise
+    op.visit -= 1
+
+
+def test_new_sampler_ops_walk_clean_and_each_fault_fails_at_its_op(tiny):
+    sp, acts = everything_on(tiny)
+    assert acts == ["step", "step", ("jump", 1), "step"]
+    hooks = {O.DdimEtaStep: f_jump_stream, O.LatentBlend: f_alpha_sigma_swapped, O.LatentRenoise: f_visit_not_advanced}
+
+    def faulty(op):
+        hook = hooks.get(type(op))
+        pre = {k: getattr(op, k).clone() for k in ("x", "x_in")} if hook else None
+        interp(op)
+        if hook:
+            hook(op, pre)
+
+    recs = P.walk(sp.prologue_ops, interp, plan="tiny")
+    new = lambda ops: [i for i, op in enumerate(ops) if type(op) in hooks]
+    # step 0 clean, every op judged: DdimEtaStep with generated noise, LatentBlend at row 0, the trace record of the blended latents
+    recs += P.walk(sp.step_ops, interp, plan="tiny")
+    assert {"DdimEtaStep", "LatentBlend", "GroupStats"} <= {r.cls for r in recs} and len(recs) == len(sp.prologue_ops) + len(sp.step_ops)
+    # step 1 (the last: the blend writes nothing), the jump, step 1 again — clean
+    for a in acts[1:]:
+        ops = sp.step_ops if a == "step" else sp.jump_ops
+        got = P.walk(ops, interp, compare=new(ops), plan="tiny")
+        assert [r.cls for r in got] == (["DdimEtaStep", "LatentBlend"] if a == "step" else ["LatentRenoise"])
+    assert (int(sp.step_ctr), int(sp.draw_ctr), int(sp.visit_ctr)) == (2, 3, 1)
+    # the same trajectory again with one fault per class: caught at its op and nowhere else
+    sp, acts = everything_on(tiny)
+    P.walk(sp.prologue_ops, interp, compare=(), plan="tiny")
+    recs = P.walk(sp.step_ops, faulty, plan="tiny", stop=False)                       # step 0: eta step and blend both write
+    failed = {r.cls: {f.condition for f in r.failures} for r in recs if r.failures}
+    assert failed == {"DdimEtaStep": {"values"}, "LatentBlend": {"values"}}, {r.name: [str(f) for f in r.failures] for r in recs if r.failures}
+    assert sum(bool(r.failures) for r in recs) == 2
+    P.walk(sp.step_ops, interp, compare=(), plan="tiny")
+    recs = P.walk(sp.jump_ops, faulty, plan="tiny", stop=False)
+    assert [(r.cls, {f.condition for f in r.failures}) for r in recs] == [("LatentRenoise", {"values"})], [str(f) for f in recs[0].failures]
+    assert "visit" in str(recs[0].failures[0])
+
+
+def run_sdpa(op, causal_shift=0):
+    """A stand-in executor of ops.Sdpa (fp32 torch; the product has only the kernel): causal_shift = -1 hides the diagonal too."""
+    B, Tq, C = op.Q.shape
+    Tk, H = op.K.shape[1], op.heads
+    h = lambda x: x.float().reshape(B, -1, H, C // H).transpose(1, 2)
+    s = h(op.Q) @ h(op.K).transpose(-1, -2) * op.scale
+    j = torch.arange(Tk)
+    if op.causal:
+        s = s.masked_fill(j[None, :] > torch.arange(Tq)[:, None] + causal_shift, -math.inf)
+    if op.klen is not None:
+        s = s.masked_fill((j[None, :] >= op.klen[:, None])[:, None, None, :], -math.inf)
+    op.O.copy_((torch.softmax(s, -1) @ h(op.V)).transpose(1, 2).reshape(B, Tq, C).to(op.O.dtype))
+
+
+def run_composite(op, erode=True):
+    """A stand-in executor of ops.ImageComposite from the product's own statement of the matte (dataset.edit_matte); erode=False: the
+    window mean of the un-eroded mask, a feather that bleeds into the regenerated region."""
+    from magicdrive_amd.dataset.regions import edit_matte
+    f = op.gen.shape[2] // op.keep.shape[1]
+    if erode:
+        w = edit_matte(op.keep, f, op.feather)
+    else:
+        r = op.feather
+        a = op.keep.repeat_interleave(f, -2).repeat_interleave(f, -1)
+        w = F.avg_pool2d(F.pad(a[:, None], (r, r, r, r), mode="replicate"), 2 * r + 1, 1)[:, 0]
+    if op.has is not None:
+        w = w * (op.has != 0).view(-1, 1, 1)
+    g = (op.gen / 2 + 0.5).clamp(0, 1).float().permute(0, 2, 3, 1)
+    w4 = w[..., None]
+    op.out.copy_(torch.where(w4 == 0, g, torch.where(w4 == 1, op.orig, torch.addcmul(g, w4, op.orig - g))))
+    if op.matte is not None:
+        op.matte.copy_(w)
+
+
+def test_sdpa_and_composite_walk_clean_and_each_fault_fails_at_its_op():
+    import composite_cases as CC
+    g = torch.Generator().manual_seed(12)
+    B, H, d, T = 2, 3, 16, 33
+    qkv = torch.randn(B, T, 3 * H * d, generator=g).to(BF)                  # the column blocks of one projection buffer, passed as they are
+    q, k, v = qkv[..., :H * d], qkv[..., H * d:2 * H * d], qkv[..., 2 * H * d:]
+    o1, o2, o3 = (torch.zeros(B, T, H * d, dtype=BF) for _ in range(3))
+    ci, r = 1, 3
+    (V, Hh, W, f), _, _ = CC.CASES[ci]
+    gen = (torch.rand(V, 3, Hh, W, generator=g) * 2.4 - 1.2).to(BF)
+    orig = torch.randint(0, 256, (V, Hh, W, 3), generator=g).float() / 255.0
+    keep = CC.keep_mask(ci)
+    out, matte = torch.zeros(V, Hh, W, 3), torch.zeros(V, Hh, W)
+    out2 = torch.zeros(V, Hh, W, 3)
+    prog = [O.Sdpa(q, k, v, o1, heads=H, scale=d ** -0.5, name="plain"),
+            O.Sdpa(q, k, v, o2, heads=H, scale=d ** -0.5, causal=True, name="causal"),
+            O.Sdpa(q, k, v, o3, heads=H, scale=d ** -0.5, klen=torch.tensor([T, 7], dtype=torch.int32), name="klen"),
+            O.ImageComposite(gen, orig, keep, out, r, matte=matte, name="feathered"),
+            O.ImageComposite(gen, orig, keep, out2, 0, has=torch.tensor([1, 0], dtype=torch.uint8), name="has")]
+
+    def clean(op):
+        (run_sdpa if isinstance(op, O.Sdpa) else run_composite)(op)
+    recs = P.walk(prog, clean)
+    assert [r_.cls for r_ in recs] == ["Sdpa"] * 3 + ["ImageComposite"] * 2
+    w = P.reference(prog[3])["matte"]
+    assert (w == 0).any() and (w == 1).any() and ((w > 0) & (w < 1)).any(), "the case must hold every regime of the matte"
+    assert torch.equal(out2[1], (gen[1] / 2 + 0.5).clamp(0, 1).float().permute(1, 2, 0)), "has == 0: the plain picture"
+
+    def faulty(op):
+        if op.name == "causal":
+            run_sdpa(op, causal_shift=-1)
+        elif op.name == "feathered":
+            run_composite(op, erode=False)
+        else:
+            clean(op)
+    recs = P.walk(prog, faulty, stop=False)
+    assert [bool(r_.failures) for r_ in recs] == [False, True, False, True, False], [[str(f_) for f_ in r_.failures] for r_ in recs]
+    assert {f_.condition for f_ in recs[1].failures} <= {"values", "finite"} and {f_.condition for f_ in recs[3].failures} == {"values"}
 
 
 # ---- the fused forms, by hand at K = 320 --------------------------------------------------------------------------------------------------

@@ -98,18 +98,70 @@ TINY_SAMPLERS = {
     "cfg_fork_trace": dict(b=1, do_cfg=True, fork=True, health="trace"),
     "unipc_given1": dict(b=1, do_cfg=True, sched="unipc", given=1),
     "scene_boxes_b2": dict(b=2, do_cfg=False, dynamic_boxes="scene"),
+    # kept regions (one ops.LatentBlend behind the scheduler op), resampling (one jump program, launched between the two steps) and
+    # stochastic DDIM (ops.DdimEtaStep in the scheduler op's place): built and loaded as tests/call_state.py does, CFG on
+    "regions_unipc": dict(call_state=dict(do_cfg=True, sched="unipc", given=1, keep_regions=True)),
+    "regions_resample": dict(call_state=dict(do_cfg=True, given=1, keep_regions=True, resample=1)),
+    "eta_regions_resample": dict(call_state=dict(do_cfg=True, given=1, keep_regions=True, resample=1, stochastic=True)),
 }
+NEW_KERNELS = {"regions_unipc": ("blend_kernel",), "regions_resample": ("blend_kernel", "renoise_kernel"),
+               "eta_regions_resample": ("blend_kernel", "renoise_kernel", "ddim_eta_kernel")}
+
+
+def call_state_sampler(nets, dtype, which):
+    import call_state as CS
+    un, cn = nets(dtype)
+    four = (nets.cfg, nets.csd, un, cn)
+    sp = CS.build_plan(four, which, nets.dev)
+    args, kw = CS.inputs(four, which, "B")
+    sp.load_inputs(*args, **kw)
+    return sp
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=KIND.values())
 @pytest.mark.parametrize("which", list(TINY_SAMPLERS))
 def test_tiny_sampler_plan_every_op(dev, tiny, which, dtype):
-    sp = sampler(tiny, dtype, L_box=5, **TINY_SAMPLERS[which])
-    recs = P.walk(sp.prologue_ops, execute, kernel=last_kernel, plan="tiny." + which)
-    for _ in range(2):
-        recs += P.walk(sp.step_ops, execute, kernel=last_kernel, plan="tiny." + which)
-    assert sp.step_ctr.item() == 2
-    judged("tiny." + which, "all", dtype, recs, len(sp.prologue_ops) + 2 * len(sp.step_ops))
+    how = TINY_SAMPLERS[which]
+    sp = call_state_sampler(tiny, dtype, how["call_state"]) if "call_state" in how else sampler(tiny, dtype, L_box=5, **how)
+    walk = lambda ops: P.walk(ops, execute, kernel=last_kernel, plan="tiny." + which)
+    recs = walk(sp.prologue_ops) + walk(sp.step_ops)
+    if sp.jump_ops:                           # step 0, one jump back to it, step 0 again: the jump op is walked too
+        recs += walk(sp.jump_ops)
+        assert (sp.step_ctr.item(), sp.visit_ctr.item()) == (0, 1)
+    recs += walk(sp.step_ops)
+    assert sp.step_ctr.item() == 2 - len(sp.jump_ops)
+    s = judged("tiny." + which, "all", dtype, recs, len(sp.prologue_ops) + 2 * len(sp.step_ops) + len(sp.jump_ops))
+    for tag in NEW_KERNELS.get(which, ()):
+        assert any(k.startswith(tag) for k in s["kernels"]), (tag, s["kernels"])
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=KIND.values())
+def test_sdpa_program_every_op(dev, dtype):
+    """A program that holds ops.Sdpa, at the shapes of tests/test_sdpa_gpu.py::test_program_executor, plus its causal and key-count forms."""
+    B, H, d, Tq, Tk = 2, 3, 80, 33, 65
+    g = torch.Generator(device="cuda").manual_seed(9)
+    q, k, v, k2, v2 = (torch.randn(B, T, H * d, generator=g, device="cuda").to(dtype) for T in (Tq, Tk, Tk, Tq, Tq))
+    new = lambda: torch.zeros(B, Tq, H * d, dtype=dtype, device=dev)
+    prog = [O.Sdpa(q, k, v, new(), heads=H, scale=d ** -0.5, name="sdpa"),
+            O.Sdpa(q, k2, v2, new(), heads=H, scale=d ** -0.5, causal=True, name="sdpa.causal"),
+            O.Sdpa(q, k, v, new(), heads=H, scale=d ** -0.5, klen=torch.tensor([Tk, 7], dtype=torch.int32, device=dev), name="sdpa.klen")]
+    s = judged("sdpa.program", "all", dtype, P.walk(prog, execute, kernel=last_kernel, plan="sdpa.program"), len(prog))
+    assert all(k.startswith("attn_vrow_kernel<") for k in s["kernels"]), s["kernels"]
+
+
+def test_composite_program_every_op(dev):
+    """A program that holds ops.ImageComposite, at the shapes of tests/test_composite_gpu.py::test_program_path, with and without the matte."""
+    import composite_cases as CC
+    from test_composite_gpu import operands
+    ci, r = 0, 1
+    gen, orig = (t.to(dev) for t in operands(ci, "bf16"))
+    keep = CC.keep_mask(ci).to(dev)
+    V, _, H, W = gen.shape
+    out = lambda: torch.zeros(V, H, W, 3, device=dev)
+    prog = [O.ImageComposite(gen, orig, keep, out(), r, name="composite"),
+            O.ImageComposite(gen, orig, keep, out(), r, matte=torch.zeros(V, H, W, device=dev), has=torch.tensor([1, 0, 1], dtype=torch.uint8, device=dev), name="composite.matte+has")]
+    s = judged("composite.program", "all", torch.bfloat16, P.walk(prog, execute, kernel=last_kernel, plan="composite.program"), len(prog))
+    assert all(k.startswith("composite_kernel") for k in s["kernels"]), s["kernels"]
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=KIND.values())

@@ -21,7 +21,7 @@ pytestmark = pytest.mark.gpu
 from helpers import check, given_view_inputs, rel_l2  # noqa: E402
 from magicdrive_amd import denoiser as DN, ops as O  # noqa: E402
 from magicdrive_amd.schedulers import resample_actions, resample_indices  # noqa: E402
-from test_latent_renoise_contract import noise_ref  # noqa: E402
+from philox_ref import noise_ref  # noqa: E402
 from test_region_keep_gpu import fractional_masks, get_pipe, inputs, one_scene  # noqa: E402
 
 
